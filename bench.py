@@ -1,6 +1,7 @@
 """Benchmark of the path-tracing hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--traversal fast|ref] [--bvh sah|reference]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +13,14 @@ two tile buffers; the timed region ends after the last frame is assembled).  K s
 synchronize fences; the max over ranks is reported.  value = W*H*spp / time in
 Msamples/s (whole job; the frame size is fixed, so scaling is "strong").
 
-Extra fields (DESIGN.md 5 derives every number):
+A plain run does only that: set-up, W warmup frames, the K timed frames, the result line (metric, value,
+unit, ms_per_step = milliseconds per timed frame, ...).  --dump-outputs DIR also writes the frame the last
+timed step produced (what a caller of the timed path receives: 3 floats per pixel, row-major) as
+DIR/frame.npy in float32, after the timed steps; a frame above 64 MB is written as a fixed, seeded sample of
+its elements.  The inputs are the same arrays on every run with the same arguments.
+
+--full adds every other measurement, each a run of its own after the timed steps (DESIGN.md 5 derives every
+number):
   roofline      -- the render kernel against the bound of the path that ran:
                    * brute-force path (scenes of <= brute_max triangles: C1/C2):
                      bound "valu", achieved = algorithmic VALU lane-operations per
@@ -394,6 +402,22 @@ def two_frames_in_flight(ctx, make_ctx, scene, ibl, cam, env, npix, spp, mb, ste
                                     "while frame k drains); not the headline, which renders one frame at a time"}
 
 
+DUMP_LIMIT = 64 << 20   # bytes --dump-outputs may write in all
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """Write each array as dirname/<name>.npy in float32; an array above its share of DUMP_LIMIT as a fixed,
+    seeded sample of its elements (ascending index order), the same on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT // max(1, len(arrays)) - 1024   # room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -406,13 +430,27 @@ def main():
     ap.add_argument("--option", action="append", default=[], help="rt_set_option KEY=VALUE (repeatable)")
     ap.add_argument("--bvh-width", type=int, default=0, choices=[0, 2, 4],
                     help="FAST tree walk layout: 2 = BVH2, 4 = 4-wide quantised (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3/C4 lines and the host-boundary timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the other measurements: the instrumented work-count launch "
+                         "and its roofline, the host-boundary and two-frames timings, the other configs, their cold "
+                         "calls and the CPU baselines (the --no-* options below drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle's timings")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="--full without the other configs' lines and the host-boundary / two-frames timings")
     ap.add_argument("--no-counts", action="store_true",
-                    help="skip the instrumented work-count launch (and the roofline it feeds): profiling passes")
+                    help="--full without the instrumented work-count launch (and the roofline it feeds): profiling "
+                         "passes")
     ap.add_argument("--check", action="store_true",
                     help="N>1: rank 0 re-renders the whole frame alone and compares it with the gathered one")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # a plain run measures the headline only; the other legs run with --full
+    extras = args.full and not args.no_extra
+    counts = args.full and not args.no_counts
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as dist
@@ -454,7 +492,8 @@ def main():
         """Render `steps` frames of one config after `warmup` untimed ones: every rank its row tile
         (rt_render_device, scene resident), rank 0 gathers the tiles over RCCL and assembles each frame
         (frame k's gather overlaps frame k+1's render: two tile buffers).  Returns (elapsed s, mean
-        kernel ms, the last assembled frame on rank 0), both times the max over ranks."""
+        kernel ms, the last frame: the one rank 0 assembled, at one rank its own tile), both times the max
+        over ranks."""
         width = int(cam[6])
         stream = torch.cuda.current_stream()
         mrows = D.max_tile_rows(npix, width, world)
@@ -510,6 +549,8 @@ def main():
             tt = torch.tensor([elapsed, kms], dtype=torch.float64, device=coll)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed, kms = float(tt[0]), float(tt[1])
+        if world == 1:
+            frame = tiles[(steps - 1) % nbuf][:3 * npix]   # one rank's tile is the whole frame
         return elapsed, kms, frame
 
     wl = Wk.CONFIGS[args.config]
@@ -520,11 +561,13 @@ def main():
     width = int(cam[6])
     stream = torch.cuda.current_stream()
     elapsed, kernel_ms, frame = run_frames(ctx, cam, env, npix, spp, mb, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frame": frame.cpu().numpy()})
 
     # work counters of the same traversal on this rank's tile (instrumented launch, not timed)
     tile_pixels = D.tile_rows(npix, width, rank, world) * width
     rf = None
-    if not args.no_counts:
+    if counts:
         cnt = ctx.count_work_detail(cam, env, npix, spp, mb, rank, world)
         rf = roofline(ctx, cnt, kernel_ms, tile_pixels, wl.name, share=tile_pixels / npix)
 
@@ -541,7 +584,7 @@ def main():
     # N > 1: the other BASELINE configs through the same multi-GPU path (row tiles + RCCL gather), so the
     # driver's per-N runs measure every config's strong scaling, not only the headline's
     multi_cfg = {}
-    if world > 1 and not args.no_extra and args.config == "C2":
+    if world > 1 and extras and args.config == "C2":
         for c, st, wu in (("C3", 2, 1), ("C4", 2, 1), ("C5", 1, 1)):
             wlc = Wk.CONFIGS[c]
             sc_c, cam_c, env_c, npix_c, spp_c, mb_c, ibl_c = wlc.inputs()
@@ -575,7 +618,7 @@ def main():
             line["frame_check"] = f"gathered {world}-rank frame vs one-device render: {frame_check}"
         if multi_cfg:
             line["configs"] = multi_cfg
-        if world == 1 and not args.no_extra:
+        if world == 1 and extras:
             # the drop-in boundary's own rate: blocking rt_render into host memory (kernel + read-back),
             # same warmup / steps as the headline
             host = np.zeros(3 * npix, np.float32)
@@ -589,13 +632,13 @@ def main():
                                      "ms_per_frame": round(dt * 1e3, 3), "steps": args.steps,
                                      "what": "rt_render (launch_Raytracing's C-ABI): kernel + copy of the frame "
                                              "into caller memory, scene already uploaded"}
-        if world == 1 and not args.no_extra:
+        if world == 1 and extras:
             line["two_frames_in_flight"] = two_frames_in_flight(ctx, make_ctx, scene, ibl, cam, env, npix, spp, mb,
                                                                 args.steps, args.warmup)
-        if world == 1 and not args.no_extra and args.config == "C2":
+        if world == 1 and extras and args.config == "C2":
             ctx.close()
             ctx = None
-            cpu = not args.no_cpu_baseline
+            cpu = cpu_leg
             line["configs"] = {"C1": time_config(make_ctx, "C1", 20, 3, cpu)}
             # C3 / C4 over 5 frames (about 0.5 / 1.4 s: their frames spread 1-3 % within a run), C5 over 2
             line["configs"].update({c: time_config(make_ctx, c, st, 1, cpu) for c, st in (("C3", 5), ("C4", 5), ("C5", 2))})
@@ -603,7 +646,7 @@ def main():
                                      "note": "the headline above"}
             for c in ("C1", "C2", "C3", "C4", "C5"):
                 line["configs"][c]["cold_call"] = cold_call(c, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             line["cpu_baseline"] = cpu_baseline(wl, scene, ibl, cam, env)
         print(json.dumps(line), flush=True)
     if world > 1:

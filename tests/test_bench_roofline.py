@@ -1,5 +1,9 @@
 """bench.py's roofline pricing (CPU): the bound it names is the path that ran, and `frac` is a
 fraction of a ceiling that path can reach (<= 1 at the measured C2/C3/C4 rates)."""
+import os
+
+import numpy as np
+
 import bench
 
 
@@ -44,3 +48,22 @@ def test_tree_walk_priced_on_cache_not_hbm():
     assert rf["achieved"] > bench.HBM_PEAK_GBS * 0.5   # the byte rate an HBM fraction would have mispriced
     assert 0.0 < rf["frac"] <= 1.0
     assert rf["hbm_measured"]["peak"] == bench.HBM_PEAK_GBS
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_of_a_large_array(tmp_path, monkeypatch):
+    """--dump-outputs: <name>.npy in float32; an array above the size limit is written as the same
+    seeded sample of its elements on every run, in index order, within the limit."""
+    a = np.arange(1000, dtype=np.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), {"frame": a})
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, a.astype(np.float32))
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1024 + 2000)      # room for 500 of the 1000 floats
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"frame": a})
+    b, c = (np.load(tmp_path / d / "frame.npy") for d in ("b", "c"))
+    np.testing.assert_array_equal(b, c)
+    assert b.dtype == np.float32 and b.size == 500
+    assert (np.diff(b) > 0).all() and np.isin(b, a.astype(np.float32)).all()
+    assert os.path.getsize(tmp_path / "b" / "frame.npy") <= bench.DUMP_LIMIT

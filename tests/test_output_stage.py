@@ -10,7 +10,7 @@ import oracle.oracle as O
 from ensem3a_openclraytracer_amd import output
 from ensem3a_openclraytracer_amd import workloads as W
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")   # the reference's IBL preview lies there
 
 
 def test_oracle_rgb8_is_numpy_savimg_arithmetic():
@@ -48,7 +48,6 @@ def test_scene_ibl_resolves_the_iblfile_key(tmp_path):
         output.scene_ibl({"IBLfile": "IBL/missing.jpg"}, str(tmp_path))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_load_ibl_matches_the_bundled_preview_fixture():
-    rgba = output.load_ibl(os.path.join(REF, "IBL", "Arches_E_PineTree_Preview.jpg"))
+    rgba = output.load_ibl(os.path.join(GOLDEN, "Arches_E_PineTree_Preview.jpg"))
     np.testing.assert_array_equal(rgba, W.ibl_preview())

@@ -1,5 +1,6 @@
 """Host data contract: the OBJ/.ini loader and the native BVH builder against the
 reference's own BVH.py export (hashes recorded from BVH.py)."""
+import gzip
 import hashlib
 import json
 import os
@@ -117,9 +118,8 @@ def test_c3_overrides():
 
 
 # ---- native OBJ import (include/rt_scene.h) ----
-# The bundled OBJ files are read from the reference checkout when it is present (this
-# container); the CPU suite only.
-SCENE_DIR = "/root/reference/ObjFiles"
+# The reference's bundled OBJ files, stored gzip-compressed (byte for byte) under tests/golden/obj.
+SCENE_DIR = os.path.join(os.path.dirname(__file__), "golden", "obj")
 
 def _same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
@@ -129,10 +129,7 @@ def _same(a, b):
 def test_native_obj_parse_matches_python(name):
     """The C++ importer returns the Python mirror's arrays bit for bit on every bundled scene."""
     from ensem3a_openclraytracer_amd import _native
-    path = os.path.join(SCENE_DIR, name + ".obj")
-    if not os.path.exists(path):
-        pytest.skip("bundled OBJ text not available")
-    with open(path) as f:
+    with gzip.open(os.path.join(SCENE_DIR, name + ".obj.gz"), "rt") as f:
         text = f.read()
     py = parse_obj(text)
     nat = _native.parse_obj(text)

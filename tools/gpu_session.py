@@ -10,9 +10,9 @@ itself (no torch import), so it may start rocprofv3 as a child.
 STEP forms (values after '=' separated by ':'):
   clock                         GPU clocks / power snapshot (amd-smi, else rocm-smi)
   pytest=EXPR                   python -m pytest tests -m gpu -k EXPR (EXPR 'all' = no -k)
-  bench=CFG[:K[:W[:OPTS]]]      bench.py --config CFG --steps K --warmup W, no CPU baseline / extras;
-                                OPTS = key=v+key=v (rt_set_option)
-  benchfull                     the default bench.py run (what the driver records)
+  bench=CFG[:K[:W[:OPTS]]]      bench.py --config CFG --steps K --warmup W --full, no CPU baseline / extras (the
+                                headline and its roofline); OPTS = key=v+key=v (rt_set_option)
+  benchfull                     bench.py --full with its defaults (every leg of the benchmark)
   smoke                         __graft_entry__.smoke()
   ab=CFGS:SPECS                 tools/ab_walk.py SPECS with AB_CFGS=CFGS (SPECS = name[@k=v+k=v]:block,...)
   abt=TILE:REPS:CFGS:SPECS      the same on rank 0's tile of a TILE-GPU run (rows 0::TILE), REPS frames timed
@@ -51,7 +51,7 @@ PMC = {
 
 
 def bench_args(cfg, steps="1", warmup="1", opts=""):
-    a = [PY, "-u", "bench.py", "--config", cfg, "--steps", steps, "--warmup", warmup, "--no-cpu-baseline",
+    a = [PY, "-u", "bench.py", "--config", cfg, "--steps", steps, "--warmup", warmup, "--full", "--no-cpu-baseline",
          "--no-extra"]
     for kv in filter(None, opts.split("+")):
         a += ["--option", kv]
@@ -75,7 +75,7 @@ def command(kind, val, tag, n):
         return bench_args(p[0], p[1] if len(p) > 1 else "2", p[2] if len(p) > 2 else "1",
                           p[3] if len(p) > 3 else ""), env
     if kind == "benchfull":
-        return [PY, "-u", "bench.py"], env
+        return [PY, "-u", "bench.py", "--full"], env
     if kind == "smoke":
         return [PY, "-u", "-c", "import __graft_entry__ as g; g.smoke()"], env
     if kind == "ab":

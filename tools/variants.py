@@ -54,7 +54,7 @@ def run(names):
         for cfg in os.environ.get("VAR_CONFIGS", "C2").split(","):
             steps = "10" if cfg == "C2" else "2"
             b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1",
-                                "--no-cpu-baseline", "--config", cfg, "--bvh", os.environ.get("BVH", "sah")],
+                                "--full", "--no-cpu-baseline", "--config", cfg, "--bvh", os.environ.get("BVH", "sah")],
                                env=env, capture_output=True, text=True, timeout=600)
             try:
                 d = json.loads(b.stdout.strip().splitlines()[-1])
