@@ -43,6 +43,58 @@ def _ibl_rgba(h_IBL) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+class Progressive(object):
+    """A frame that takes more samples (``KernelLauncher.begin_progressive``; rt_accum_* of rt_api.h).
+
+    Every ``add`` returns a finished frame at the samples done so far -- the frame ``launch_Raytracing``
+    renders at that ``spp``, bit for bit -- and costs only the samples it adds.
+    """
+
+    def __init__(self, ctx: "_native.Context", imgDim: int):
+        self._ctx = ctx
+        self._n = int(imgDim)
+        self._open = True
+
+    def _out(self, out, dtype):
+        if not self._open:
+            raise RuntimeError("the progressive render is closed (or was replaced by a later begin_progressive)")
+        if out is None:
+            return np.zeros(3 * self._n, dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or not out.flags.c_contiguous:
+            raise TypeError(f"out must be a C-contiguous {np.dtype(dtype).name} numpy array")
+        if out.size < 3 * self._n:
+            raise ValueError(f"out has {out.size} elements, needs 3*imgDim = {3 * self._n}")
+        return out
+
+    def add(self, spp: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``spp`` (>= 1) more samples of every pixel; the frame (float32 ``[3*imgDim]``, into ``out`` if given)."""
+        out = self._out(out, np.float32)
+        self._ctx.accum_add(int(spp), out=out.reshape(-1))
+        return out
+
+    def add_rgb8(self, spp: int, gamma: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``add`` with the 8-bit output stage of ``launch_Raytracing_rgb8`` on the device (a preview)."""
+        out = self._out(out, np.uint8)
+        self._ctx.accum_add_rgb8(int(spp), gamma=gamma, out=out.reshape(-1))
+        return out
+
+    def image(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The frame at the samples done; nothing is rendered."""
+        out = self._out(out, np.float32)
+        self._ctx.accum_read(out=out.reshape(-1))
+        return out
+
+    @property
+    def samples(self) -> int:
+        """Samples done per pixel (-1 once closed)."""
+        return self._ctx.accum_samples() if self._open else -1
+
+    def close(self) -> None:
+        if self._open:
+            self._open = False
+            self._ctx.accum_end()
+
+
 class KernelLauncher(object):
     """``KernelLauncher(context, platform, device, queue)``.
 
@@ -153,6 +205,29 @@ class KernelLauncher(object):
         self._upload_env(h_IBL)
         self._ctx.render_rgb8(cam[:10], env[:5], imgDim, int(spp), int(maxBounce), gamma=gamma,
                               out=h_img_out.reshape(-1))
+
+    def begin_progressive(self, h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_light_data,
+                          h_BVH, h_cam, h_envData, imgDim, maxBounce, h_IBL) -> "Progressive":
+        """Open a progressive render of the frame ``launch_Raytracing`` would render from these arguments
+        (its order, without ``h_img_out`` and ``spp``): the returned :class:`Progressive` adds samples to
+        the frame, and after adds of ``a`` and ``b`` samples the frame is, bit for bit, ``launch_Raytracing``
+        at ``spp = a + b``.  One per launcher at a time: a second call replaces the first.  Uploading another
+        scene or IBL (a ``launch_Raytracing`` with other arrays) invalidates it: its next ``add`` raises
+        :class:`~._native.NativeError`; a call with the same arrays (an upload-cache hit) does not."""
+        imgDim = int(imgDim)
+        cam = _native.f32(h_cam).reshape(-1)
+        env = _native.f32(h_envData).reshape(-1)
+        if cam.size < 10 or env.size < 5:
+            raise ValueError("h_cam needs 10 floats and h_envData 5")
+        if h_light_data is not None:
+            np.asarray(h_light_data)  # accepted for signature compatibility (unused by the kernel)
+        self._upload_scene(h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_BVH)
+        self._upload_env(h_IBL)
+        if getattr(self, "_progressive", None) is not None:
+            self._progressive._open = False   # replaced: the context holds one accumulation
+        self._ctx.accum_begin(cam[:10], env[:5], imgDim, int(maxBounce))
+        self._progressive = Progressive(self._ctx, imgDim)
+        return self._progressive
 
     def launch_ImgProcessing(self, h_src, h_out, SIZE):
         """Gamma 2.2 of ``ImgProcessing.cl``: ``h_out[k] = min(h_src[k], 1) ** 2.2`` for ``k < 3*SIZE*SIZE``."""

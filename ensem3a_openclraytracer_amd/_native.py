@@ -21,12 +21,17 @@ RT_TRAVERSAL_FAST = 0
 RT_TRAVERSAL_REF = 1
 RT_BVH_REFERENCE = 0
 RT_BVH_SAH = 1
+RT_ERR_ARG = 1
+RT_ERR_STATE = 3
+RT_ACCUM_MAX_SAMPLES = 1 << 24   # rt_api.h: the most samples per pixel an accumulation may reach
 
 # Every symbol of include/rt_api.h and include/rt_debug.h (checked by tests).
 EXPORTED = (
     "rt_create", "rt_destroy", "rt_last_error", "rt_set_scene", "rt_set_env", "rt_set_option",
     "rt_render", "rt_render_device", "rt_tile_rows", "rt_count_work", "rt_count_work_detail", "rt_work_bytes", "rt_gamma",
     "rt_render_rgb8", "rt_rgb8_device", "rt_rgb8",
+    "rt_accum_begin", "rt_accum_add", "rt_accum_add_rgb8", "rt_accum_read", "rt_accum_samples", "rt_accum_end",
+    "rt_accum_begin_device", "rt_accum_add_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
@@ -101,6 +106,14 @@ def lib():
             "rt_render_rgb8": (_i32, [_c_p, _c_p, _c_p, _i64, _i32, _i32, _i32, _c_p]),
             "rt_rgb8_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, _c_p]),
             "rt_rgb8": (_i32, [_c_p, _c_p, _c_p, _i64, _i32]),
+            "rt_accum_begin": (_i32, [_c_p, _c_p, _c_p, _i64, _i32]),
+            "rt_accum_add": (_i32, [_c_p, _i32, _c_p]),
+            "rt_accum_add_rgb8": (_i32, [_c_p, _i32, _i32, _c_p]),
+            "rt_accum_read": (_i32, [_c_p, _c_p]),
+            "rt_accum_samples": (_i64, [_c_p]),
+            "rt_accum_end": (_i32, [_c_p]),
+            "rt_accum_begin_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, _i32, _i32]),
+            "rt_accum_add_device": (_i32, [_c_p, _i32, _i32, _c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -288,6 +301,54 @@ class Context:
         self._check(lib().rt_render_rgb8(self.handle, ptr(c), ptr(e), int(npix), int(spp), int(max_bounce),
                                          int(bool(gamma)), out.ctypes.data))
         return out
+
+    # -- progressive accumulation (rt_accum_*): adds of a then b samples give the one-shot frame at a + b --
+    def accum_begin(self, cam, env, npix: int, max_bounce: int) -> None:
+        c, e = f32(cam), f32(env)
+        if c.size != 10 or e.size != 5:
+            raise ValueError("cam must have 10 floats and envData 5")
+        self._check(lib().rt_accum_begin(self.handle, ptr(c), ptr(e), int(npix), int(max_bounce)))
+        self._accum_npix = int(npix)
+
+    def _accum_out(self, out, dtype) -> np.ndarray:
+        n = 3 * getattr(self, "_accum_npix", 0)
+        if out is None:
+            return np.zeros(n, dtype=dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or not out.flags.c_contiguous or out.size < n:
+            raise ValueError(f"output must be a contiguous {np.dtype(dtype).name} array of 3*imgDim elements")
+        return out
+
+    def accum_add(self, spp: int, out: np.ndarray = None) -> np.ndarray:
+        """``spp`` more samples of every pixel; returns the frame at the samples done (float32[3*npix])."""
+        out = self._accum_out(out, np.float32)
+        self._check(lib().rt_accum_add(self.handle, int(spp), out.ctypes.data))
+        return out
+
+    def accum_add_rgb8(self, spp: int, gamma: bool = False, out: np.ndarray = None) -> np.ndarray:
+        out = self._accum_out(out, np.uint8)
+        self._check(lib().rt_accum_add_rgb8(self.handle, int(spp), int(bool(gamma)), out.ctypes.data))
+        return out
+
+    def accum_read(self, out: np.ndarray = None) -> np.ndarray:
+        out = self._accum_out(out, np.float32)
+        self._check(lib().rt_accum_read(self.handle, out.ctypes.data))
+        return out
+
+    def accum_samples(self) -> int:
+        return int(lib().rt_accum_samples(self.handle))
+
+    def accum_end(self) -> None:
+        self._check(lib().rt_accum_end(self.handle))
+        self._accum_npix = 0
+
+    def accum_begin_device(self, cam, env, npix, max_bounce, row0, row_step, device_index: int = 0) -> None:
+        c, e = f32(cam), f32(env)
+        self._check(lib().rt_accum_begin_device(self.handle, int(device_index), ptr(c), ptr(e), int(npix),
+                                                int(max_bounce), int(row0), int(row_step)))
+
+    def accum_add_device(self, spp: int, d_out_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_add_device(self.handle, int(device_index), int(spp), _c_p(int(d_out_ptr)),
+                                              _c_p(int(stream_ptr)) if stream_ptr else None))
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

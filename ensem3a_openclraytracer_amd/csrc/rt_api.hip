@@ -52,6 +52,14 @@ struct Device {
     DevBuf pilot;                 // two-pass launches: per-pixel state, cost and order (FrameParams::pilot_*)
     DevBuf spec;                  // speculation: the trails' sample logs (FrameParams::spec_log)
     DevBuf slice;                 // sample slices: per-pixel state + samples done (FrameParams::slice_*)
+    // Progressive accumulation of this slot's tile (rt_accum_*): the per-pixel state in a buffer of its own
+    // (FrameParams::accum_state) -- no other entry point touches it -- and the frame it accumulates
+    DevBuf accum;
+    bool acc_open = false;
+    bool acc_valid = false;       // false once the scene, the environment or the hits' definition changed
+    float acc_cam[10] = {0}, acc_env[5] = {0};
+    int64_t acc_npix = 0, acc_nloc = 0, acc_samples = 0;
+    int acc_max_bounce = 0, acc_row0 = 0, acc_row_step = 1;
     char* host_stage = nullptr;   // pinned staging for rt_render / rt_render_rgb8
     int* host_pick = nullptr;     // pinned: a two-pass launch's pass-2 pick, read back (rt::RenderPending)
     size_t host_stage_bytes = 0;
@@ -95,6 +103,7 @@ struct rt_ctx {
     int wdq = 1;          // 4-wide walk: origin-folded dequantisation where the builder's gap covers the frame (option "wdq")
     int handout = -1;     // pixel hand-out: 0 = interleaved chunks, 1 = a contiguous block per XCD group, -1 = auto
     int slices = -1;      // one-pass tree-walk launches: sample slices per pixel (FrameParams::slices; 0 off, -1 auto)
+    bool accum_host = false;   // the open accumulation is rt_accum_begin's: every slot holds its rows of one frame
     // host wall times of the last calls (rt_debug_timings), ms: rt_set_scene's validation + packing and its
     // uploads (+ the per-triangle frame kernel), rt_set_env (upload + texel-sum kernel), rt_render's
     // blocking render + read-back
@@ -277,6 +286,11 @@ int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, i
     return RT_OK;
 }
 
+// rt_set_scene, rt_set_env and the options that redefine a hit: an open accumulation cannot be continued
+void invalidate_accum(rt_ctx* ctx) {
+    for (auto& d : ctx->devs) d.acc_valid = false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -328,7 +342,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.pending) (void)hipEventSynchronize(d.done);
         if (d.stream) (void)hipStreamSynchronize(d.stream);
         for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
-                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice})
+                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum})
             release(*b);
         if (d.host_stage) (void)hipHostFree(d.host_stage);
         if (d.host_pick) (void)hipHostFree(d.host_pick);
@@ -346,6 +360,7 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         if (value != RT_TRAVERSAL_FAST && value != RT_TRAVERSAL_REF)
             return set_err(ctx, RT_ERR_ARG, "traversal must be 0 (fast) or 1 (ref)");
         ctx->traversal = (int)value;
+        invalidate_accum(ctx);
         return RT_OK;
     }
     if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max")) {
@@ -455,6 +470,7 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
     if (!std::strcmp(key, "ref_stack")) {
         if (value < 20 || value > 64) return set_err(ctx, RT_ERR_ARG, "ref_stack must be in 20..64 (20 = the reference's)");
         ctx->ref_stack = (int)value;
+        invalidate_accum(ctx);
         return RT_OK;
     }
     if (!std::strcmp(key, "slices")) {
@@ -498,6 +514,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, ctx->bvh_layout,
                                      ctx->brute_max, msg, why);
     if (rc != RT_OK) return set_err(ctx, rc, "%s", msg.c_str());
+    invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
     for (auto& d : ctx->devs) {
         HIP_OR_RET(ctx, hipSetDevice(d.id));
@@ -536,6 +553,7 @@ int rt_set_env(rt_ctx* ctx, const uint8_t* rgba, int w, int h) {
     if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
     if (!rgba || w <= 0 || h <= 0) return set_err(ctx, RT_ERR_ARG, "bad IBL image (%d x %d)", w, h);
     const size_t bytes = (size_t)w * h * 4;
+    invalidate_accum(ctx);
     const auto t0 = std::chrono::steady_clock::now();
     for (auto& d : ctx->devs) {
         HIP_OR_RET(ctx, hipSetDevice(d.id));
@@ -570,6 +588,7 @@ namespace {
 constexpr int kSlicesWide = 8;
 constexpr int kSlicesWideSmall = 12;
 constexpr int64_t kSlicesMinPerLane = 4;
+constexpr int kAccumSliceMin = 8;
 
 // Two-pass launches (FrameParams::pass): FAST tree-walk renders of tiles with more pixels than the
 // device keeps lanes resident get a pilot pass of spp / 8 samples (option "pilot": -1 auto, 0 off,
@@ -654,7 +673,7 @@ namespace {
 // N=4 1,395 / 1,273 / 1,221 / 1,197, N=2 2,536 / 2,409 / 2,361 / 2,343, N=1 4,796 / 4,692 / 4,642 / 4,648
 // (the wave cap of 6 instead: 838 / 1,444 / 2,651 / 5,066).  Sets fp's slice fields, sizes the device's
 // state buffer and zeroes the samples-done words on stream s (the launch's stream).
-hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t s) {
+hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t s, int accum_base = -1) {
     fp.slices = 0;
     if (effective_traversal(ctx) != RT_TRAVERSAL_FAST || fp.nloc <= 0 || ctx->hs.nbrute > 0 || fp.resume_min <= 0 ||
         ctx->slices == 0)
@@ -669,7 +688,12 @@ hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t
     if (ctx->slices < 0 && use_wide(ctx) &&
         fp.nloc < kSlicesMinPerLane * (int64_t)std::max(d.cus, 1) * rt::kWideWaves * 4 * 64)
         k = kSlicesWideSmall;
-    k = std::min(k, (fp.spp - std::max(fp.pilot, 0)) / 2);   // every slice at least two samples
+    // every slice at least two samples; accum_base >= 0: an add of a progressive accumulation, whose slices
+    // split the samples it adds -- chosen automatically, at least kAccumSliceMin each (below that the
+    // hand-offs cost more than the shorter tail gives back)
+    const int todo = fp.spp - std::max(fp.pilot, 0) - std::max(accum_base, 0);
+    k = std::min(k, todo / 2);
+    if (accum_base >= 0 && ctx->slices < 0) k = std::min(k, todo / kAccumSliceMin);
     if (k <= 1 || (int64_t)fp.nloc * k >= ((int64_t)1 << 32)) return hipSuccess;
     const size_t n = (size_t)fp.nloc;
     const size_t need = n * 32 + n * sizeof(uint32_t);
@@ -828,7 +852,208 @@ int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t n
     }
     return RT_OK;
 }
+
+// ---- progressive accumulation (rt_accum_*) ----
+int accum_close_slot(rt_ctx* ctx, Device& d) {
+    d.acc_open = false;
+    d.acc_valid = false;
+    d.acc_samples = 0;
+    if (!d.accum.p) return RT_OK;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    if (d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));   // an add in flight still uses the state
+    release(d.accum);
+    return RT_OK;
+}
+
+int accum_slot_usable(rt_ctx* ctx, const Device& d, const char* what) {
+    if (!d.acc_open) return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open", what);
+    if (!d.acc_valid)
+        return set_err(ctx, RT_ERR_STATE, "%s: the accumulation was invalidated (scene, environment, \"traversal\" "
+                       "or \"ref_stack\" changed since it began)", what);
+    return RT_OK;
+}
+
+int accum_check_add(rt_ctx* ctx, const Device& d, int spp) {
+    int st = accum_slot_usable(ctx, d, "rt_accum_add");
+    if (st) return st;
+    if (spp < 1) return set_err(ctx, RT_ERR_ARG, "rt_accum_add: spp must be >= 1, got %d", spp);
+    if (d.acc_samples + (int64_t)spp > RT_ACCUM_MAX_SAMPLES)
+        return set_err(ctx, RT_ERR_ARG, "rt_accum_add: %lld + %d samples exceed RT_ACCUM_MAX_SAMPLES (%d)",
+                       (long long)d.acc_samples, spp, (int)RT_ACCUM_MAX_SAMPLES);
+    return RT_OK;
+}
+
+// the host forms: add spp samples on every slot (read: resolve the state instead, nothing rendered), then read
+// the frame back as render_host_ does (rgb8 >= 0: quantised on the devices first); out may be NULL for an add
+int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char* what) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
+    const int nd = (int)ctx->devs.size();
+    for (int k = 0; k < nd; ++k) {
+        const int st = read ? accum_slot_usable(ctx, ctx->devs[k], what) : accum_check_add(ctx, ctx->devs[k], spp);
+        if (st) return st;
+    }
+    if (read && ctx->devs[0].acc_samples == 0)
+        return set_err(ctx, RT_ERR_STATE, "%s: the accumulation has no samples yet", what);
+    if (read && !out) return set_err(ctx, RT_ERR_ARG, "output must not be NULL");
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    const size_t elem = rgb8 >= 0 ? 1 : sizeof(float);
+    // every slot's launch is enqueued before the host waits for any
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        const size_t bytes = (size_t)d.acc_nloc * 3 * elem;
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, ensure(d.out, std::max<size_t>((size_t)d.acc_nloc * 3 * sizeof(float), 16)));
+        if (out && d.host_stage_bytes < bytes) {
+            if (d.host_stage) HIP_OR_RET(ctx, hipHostFree(d.host_stage));
+            d.host_stage = nullptr;
+            d.host_stage_bytes = 0;
+            HIP_OR_RET(ctx, hipHostMalloc((void**)&d.host_stage, bytes, hipHostMallocDefault));
+            d.host_stage_bytes = bytes;
+        }
+        if (!read) {
+            const int st = rt_accum_add_device(ctx, k, spp, (float*)d.out.p, d.stream);
+            if (st) return st;
+        } else if (d.acc_nloc > 0) {
+            HIP_OR_RET(ctx, order_after_last(d, d.stream));
+            HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, (float*)d.out.p, d.acc_nloc, d.stream));
+            HIP_OR_RET(ctx, mark_launch(d, d.stream));
+        }
+        if (!out || bytes == 0) continue;
+        const void* src = d.out.p;
+        if (rgb8 >= 0) {
+            HIP_OR_RET(ctx, ensure(d.out8, bytes));
+            HIP_OR_RET(ctx, rt::launch_rgb8((const float*)d.out.p, (uint8_t*)d.out8.p, d.acc_nloc * 3, rgb8 == 1,
+                                            d.stream));
+            src = d.out8.p;
+        }
+        HIP_OR_RET(ctx, hipMemcpyAsync(d.host_stage, src, bytes, hipMemcpyDeviceToHost, d.stream));
+    }
+    char* dst = static_cast<char*>(out);
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+        if (!out) continue;
+        const int64_t rows = rt_tile_rows(npix, W, k, nd);
+        if (nd == 1) {
+            par_copy(dst, d.host_stage, (size_t)npix * 3 * elem);
+            continue;
+        }
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t first = ((int64_t)k + r * nd) * W;
+            const int64_t count = std::min<int64_t>(W, npix - first);
+            std::memcpy(dst + 3 * first * elem, d.host_stage + 3 * r * W * elem, (size_t)count * 3 * elem);
+        }
+    }
+    return RT_OK;
+}
 }  // namespace
+
+int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5], int64_t npix,
+                          int max_bounce, int row0, int row_step) {
+    rt::FrameParams fp;
+    int st = check_frame(ctx, cam, env, npix, 0, row0, row_step, &fp);
+    if (st) return st;
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
+    Device& d = ctx->devs[device_index];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    d.acc_open = false;   // replaces the slot's accumulation
+    d.acc_valid = false;
+    const size_t need = std::max<size_t>((size_t)fp.nloc * 2 * sizeof(float4), 16);
+    // growing frees the old buffer from the host: the last launch (any stream) may still use it
+    if (d.accum.bytes < need && d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));
+    HIP_OR_RET(ctx, ensure(d.accum, need));
+    std::memcpy(d.acc_cam, cam, sizeof d.acc_cam);
+    std::memcpy(d.acc_env, env, sizeof d.acc_env);
+    d.acc_npix = npix;
+    d.acc_nloc = fp.nloc;
+    d.acc_max_bounce = max_bounce;
+    d.acc_row0 = row0;
+    d.acc_row_step = row_step;
+    d.acc_samples = 0;
+    d.acc_open = true;
+    d.acc_valid = true;
+    ctx->accum_host = false;
+    return RT_OK;
+}
+
+int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    Device& d = ctx->devs[device_index];
+    int st = accum_check_add(ctx, d, spp);
+    if (st) return st;
+    rt::FrameParams fp;
+    // the frame as begun, at the samples done after this add, under the options as they are now
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, (int)(d.acc_samples + spp), d.acc_row0, d.acc_row_step, &fp);
+    if (st) return st;
+    if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
+    fp.max_bounce = d.acc_max_bounce;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    // an add is one pass: no pilot pass and no trails (whatever "pilot" and "spec" say); sample slices as
+    // rt_render_device would take them, over the samples this add runs
+    HIP_OR_RET(ctx, setup_slices(ctx, d, fp, s, (int)d.acc_samples));
+    if (fp.nloc > 0) {
+        d.acc_valid = false;   // (an error below leaves the state undefined)
+        HIP_OR_RET(ctx, rt::launch_accum(dev_scene(ctx, d), fp, (float4*)d.accum.p, (int)d.acc_samples,
+                                         effective_traversal(ctx), ctx->block, d_out, (unsigned int*)d.work.p, s));
+        HIP_OR_RET(ctx, mark_launch(d, s));
+        d.acc_valid = true;
+    }
+    d.acc_samples += spp;
+    return RT_OK;
+}
+
+int rt_accum_begin(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int max_bounce) {
+    rt::FrameParams fp;
+    int st = check_frame(ctx, cam, env, npix, 0, 0, 1, &fp);
+    if (st) return st;
+    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
+    const int nd = (int)ctx->devs.size();
+    for (int k = 0; k < nd; ++k) {
+        st = rt_accum_begin_device(ctx, k, cam, env, npix, max_bounce, k, nd);
+        if (st) return st;
+    }
+    ctx->accum_host = true;
+    return RT_OK;
+}
+
+int rt_accum_add(rt_ctx* ctx, int spp, float* out_rgb) {
+    return accum_host(ctx, spp, false, out_rgb, -1, "rt_accum_add");
+}
+
+int rt_accum_add_rgb8(rt_ctx* ctx, int spp, int gamma, uint8_t* out_rgb8) {
+    if (ctx && gamma != 0 && gamma != 1) return set_err(ctx, RT_ERR_ARG, "gamma must be 0 or 1");
+    return accum_host(ctx, spp, false, out_rgb8, gamma, "rt_accum_add_rgb8");
+}
+
+int rt_accum_read(rt_ctx* ctx, float* out_rgb) { return accum_host(ctx, 0, true, out_rgb, -1, "rt_accum_read"); }
+
+int64_t rt_accum_samples(rt_ctx* ctx) {
+    if (!ctx) return -1;
+    for (const auto& d : ctx->devs)
+        if (d.acc_open) return d.acc_samples;
+    return -1;
+}
+
+int rt_accum_end(rt_ctx* ctx) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    int rc = RT_OK;
+    for (auto& d : ctx->devs) {
+        const int st = accum_close_slot(ctx, d);
+        if (st && !rc) rc = st;
+    }
+    ctx->accum_host = false;
+    return rc;
+}
 
 int rt_render(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,
               float* out_rgb) {

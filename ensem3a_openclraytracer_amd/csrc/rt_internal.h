@@ -133,6 +133,15 @@ struct FrameParams {
     int32_t log_cap;
     int32_t* log_count;
 };
+// Progressive accumulation (rt_accum_*): an add runs the ACC instantiations of the render kernels, which are
+// always one pass (pass = 0) and read two of the pilot fields in a meaning of their own, so that FrameParams --
+// and with it the kernel arguments and the code of the one-shot kernels -- is what it was without them:
+//   pilot        the samples earlier adds have done (the launch runs samples pilot .. spp - 1 of every pixel);
+//   pilot_state  the accumulation's state buffer (the context's, one per device slot; never d.pilot), in the
+//                pilot's layout: two float4 per tile pixel, acc.xyz | kc, seed0 seed1 tc s.
+// A pixel's lane restores from it (pilot > 0) and, after sample spp - 1, saves back; out receives
+// clamp(acc / spp).  tc is the reference triangle index and kc the hit distance every engine computes alike,
+// so any engine continues any other's state.
 
 // A two-pass launch's second pass, waiting for the first: pass 2 launches the kernel the device picked
 // (pilot_team_pick_kernel) from the pixels pass 1 left, so the host reads that pick back first.
@@ -153,6 +162,13 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
                          RenderPending* pend = nullptr);
 hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, float* d_out, unsigned int* d_work,
                                 hipStream_t stream, RenderPending& pend);
+// One add of a progressive accumulation (state, base: see above; fp: a one-pass frame, fp.spp = the samples done
+// after the add): one pass of the ACC instantiation of the kernel launch_render would pick for fp (sample
+// slices as set in fp; no pilot pass, no trails).
+hipError_t launch_accum(const DevScene& sc, const FrameParams& fp, float4* state, int base, int traversal, int block,
+                        float* d_out, unsigned int* d_work, hipStream_t stream);
+// out[3 p ..] = clamp(acc / s) of the n pixels of an accumulation state (rt_accum_read)
+hipError_t launch_accum_resolve(const float4* state, float* d_out, int64_t n, hipStream_t stream);
 hipError_t launch_prep_frames(const DevScene& sc, float4* frame, hipStream_t stream);
 // the IBL's 2x2 texel-sum table (DevScene::ibl_sum) from the RGBA8 image: (w + 1) x (h + 1) words
 hipError_t launch_ibl_sum(const uchar4* rgba, int w, int h, uint32_t* sum, hipStream_t stream);

@@ -30,13 +30,25 @@ namespace rt {
 
 namespace {
 
+// A pixel's state between two adds of a progressive accumulation (the ACC instantiations; layout of
+// FrameParams::pilot_state): the sum, the cached camera hit, the RNG words and the samples done
+__device__ __forceinline__ void save_state(float4* __restrict__ st, int p, rtm_f3 acc, float kc, uint32_t seed0,
+                                           uint32_t seed1, int tc, int s) {
+    st[2 * (int64_t)p] = make_float4(acc.x, acc.y, acc.z, kc);
+    st[2 * (int64_t)p + 1] =
+        make_float4(__uint_as_float(seed0), __uint_as_float(seed1), __int_as_float(tc), __int_as_float(s));
+}
+
 // One persistent lane = one pixel at a time.  Lanes that finish their pixel
 // take the next pixel index from a global counter: the wave ballots the lanes
 // that need work, one lane adds the count to the counter, and each lane takes
 // base + (its rank among the requesting lanes) -- so no lane idles while the
 // rest of its wave finishes a slower pixel.  Per loop iteration every busy
 // lane traces exactly one ray (primary, bounce or sun ray).
-template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE = 0>
+// ACC: an add of a progressive accumulation (rt_internal.h: F.pilot_state its state, F.pilot the samples done,
+// one pass) -- instantiations of their own, so that
+// the one-shot kernels keep their code and registers
+template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE = 0, bool ACC = false>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
 // spills, the instrumented (COUNT) ones spill a few registers to scratch.
@@ -181,6 +193,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                         so = rtm_v3(1, 1, 1);
                         phase = s >= spp ? FETCH : PREP;   // finished in pass 1: already written
                     }
+                    if constexpr (ACC) if (F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
+                        const float4 a = F.pilot_state[2 * (int64_t)p], b = F.pilot_state[2 * (int64_t)p + 1];
+                        acc = rtm_v3(a.x, a.y, a.z);
+                        kc = a.w;
+                        seed0 = __float_as_uint(b.x);
+                        seed1 = __float_as_uint(b.y);
+                        tc = __float_as_int(b.z);
+                        s = __float_as_int(b.w);
+                        tri = tc; j = 0;
+                        so = rtm_v3(1, 1, 1);
+                        phase = PREP;
+                    }
                 } else {
                     // past the tile, or a padding pixel of a partial last row (its hand-out group, or pass 2's
                     // cost order, may still hold real pixels): the lane retires once the queue is dry
@@ -253,6 +277,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                     phase = FETCH;
                     if (team_leader) store_pixel(out, p, acc, spp);
                     if (F.pass == 1) save_pilot();
+                    if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                 } else if (F.pass == 1 && s >= F.pilot) {
                     save_pilot();
                     phase = FETCH;
@@ -344,6 +369,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             if (s >= spp) {
                 if (team_leader) store_pixel(out, p, acc, spp);
                 if (F.pass == 1) save_pilot();
+                if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                 phase = FETCH;
             } else if (F.pass == 1 && s >= F.pilot) {
                 save_pilot();
@@ -388,7 +414,7 @@ constexpr size_t kStepMaxBytes = 16u << 20;
 // TS > 1: teams of TS lanes per pixel walk each ray together (team_step; BVH2 item steps only).
 // WIDE: 0 = the BVH2 walk, 1 = the 4-wide walk, 2 = the 4-wide walk with origin-folded dequantisation
 // (wide_node DQ; launch_fast picks it when the camera lies within DevScene::wdq_omax)
-template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS = 1>
+template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS = 1, bool ACC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? kWideWaves : 4))) render_resume_kernel(DevScene S, FrameParams F, float* __restrict__ out,
                                                       unsigned long long* __restrict__ counts,
                                                       unsigned int* __restrict__ work_counter,
@@ -397,7 +423,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     const int B = blockDim.x;
     // two-pass launches are BVH2-only (the 4-wide walk's pilot measured slower, rt_api.hip setup_pilot):
     // the 4-wide instantiations are one-pass and carry none of the pass code
-    const int pass = WIDE ? 0 : F.pass;
+    const int pass = (WIDE || ACC) ? 0 : F.pass;   // (an accumulation's add is one pass)
     Cnt c{};
     const LaunchConst& C = *lconst;
     const float4* nodes = S.nodes;
@@ -459,7 +485,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     // (one-pass launches, and pass 2 of a pilot launch: the samples after the pilot's sb = F.pilot; slice k
     // of a pixel ends at sb + (k + 1) (spp - sb) / nsl)
     const unsigned nsl = (TS == 1 && F.slices > 1 && pass != 1) ? (unsigned)F.slices : 1u;
-    const int sb = pass == 2 ? F.pilot : 0;
+    const int sb = (ACC || pass == 2) ? F.pilot : 0;   // (ACC: the samples of earlier adds, rt_internal.h)
     auto slice_end = [&](unsigned k) { return sb + (int)((k + 1u) * (unsigned)(spp - sb) / nsl); };
     int lim = spp;
     // The deterministic prefix of the pixel's samples (FrameParams::fixed_point; BVH2 walk): a sample's
@@ -483,6 +509,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
 
     auto write_pixel = [&]() __attribute__((always_inline)) {
         if (team_leader) store_pixel(out, p, acc, spp);
+        // ACC: the pixel's last sample of this add: its state for the next add
+        if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
     };
     // pass 1 (FrameParams::pass): after the pilot samples, save the pixel's state for pass 2; the
     // pixel is written (and its cost set to 0) when all its samples are done
@@ -609,6 +637,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
                         lim = slice_end(0);
                         phase = s >= spp ? FETCH : PREP;   // finished in pass 1: already written
                         if (nsl > 1 && s >= spp) save_slice();   // ... and its later slices have nothing to do
+                    } else if (ACC && F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
+                        const float4 a = F.pilot_state[2 * (int64_t)p], b = F.pilot_state[2 * (int64_t)p + 1];
+                        acc = rtm_v3(a.x, a.y, a.z);
+                        kc = a.w;
+                        seed0 = __float_as_uint(b.x);
+                        seed1 = __float_as_uint(b.y);
+                        tc = __float_as_int(b.z);
+                        s = __float_as_int(b.w);
+                        tri = tc; j = 0;
+                        so = rtm_v3(1, 1, 1);
+                        drew = false;
+                        lim = slice_end(0);
+                        phase = PREP;
                     } else {
                         lim = slice_end(0);
                         start(C.position, cd);
@@ -894,7 +935,7 @@ __global__ void pilot_team_pick_kernel(const unsigned* __restrict__ left, int64_
 }
 
 template <int TRAV, bool COUNT, bool LOG, bool SMEM = false, bool RESUME = false, bool OVF = false,
-          bool BRUTE = false, bool STEP = true, int WIDE = 0>
+          bool BRUTE = false, bool STEP = true, int WIDE = 0, bool ACC = false>
 hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float* d_out, unsigned long long* d_counts,
                     unsigned int* d_work, hipStream_t stream) {
     // FAST: int2 entries; the brute-force path of small scenes needs no stack
@@ -910,8 +951,8 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     int dev = 0, cus = 0, per_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const void* kfn = RESUME ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE>
-                             : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0>;
+    const void* kfn = RESUME ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>
+                             : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>;
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, block, lds);
     if (e != hipSuccess) return e;
     // blocks per CU for at most max_waves waves per SIMD (4 SIMDs per CU)
@@ -947,9 +988,9 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     // the team instantiations (TS = 2, 4, 8) and their own occupancy
     auto team_fn = [&](int ts) -> const void* {
         if (!kTeamable) return nullptr;
-        return ts == 2 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1>
-             : ts == 4 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1>
-                       : (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1>;
+        return ts == 2 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1, ACC>
+             : ts == 4 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1, ACC>
+                       : (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1, ACC>;
     };
     auto team_grid = [&](int ts, int64_t* g) -> hipError_t {
         int per_cu_w = 0;
@@ -963,7 +1004,7 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
         if (e != hipSuccess) return e;
     }
     // teams run their own instantiation (the ts = 1 kernel keeps the scalar box loop)
-    const void* tfn = (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0>;
+    const void* tfn = (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>;
     if (BRUTE && f.team > 1) {
         int per_cu_t = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_t, tfn, block, lds);
@@ -978,25 +1019,25 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     LaunchConst* lc = reinterpret_cast<LaunchConst*>(reinterpret_cast<char*>(d_work) + kConstOffset);
     hipLaunchKernelGGL(make_const_kernel, dim3(1), dim3(64), 0, stream, f, lc);
     if (kTeamable && wteam == 2)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1>),
+        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1, ACC>),
                            dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
                            (const LaunchConst*)lc);
     else if (kTeamable && wteam == 4)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1>),
+        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1, ACC>),
                            dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
                            (const LaunchConst*)lc);
     else if (kTeamable && wteam == 8)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1>),
+        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1, ACC>),
                            dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
                            (const LaunchConst*)lc);
     else if (RESUME)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE>), dim3((unsigned)grid), dim3(block), lds, stream,
+        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>), dim3((unsigned)grid), dim3(block), lds, stream,
                            sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else if (BRUTE && f.team > 1)
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0>), dim3((unsigned)grid),
+        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>), dim3((unsigned)grid),
                            dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0>), dim3((unsigned)grid),
+        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>), dim3((unsigned)grid),
                            dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     return hipGetLastError();
 }
@@ -1042,6 +1083,10 @@ __global__ void __launch_bounds__(256) debug_trace_kernel(DevScene S, const floa
 
 }  // namespace
 
+// rt_accum.hip compiles this file again with RT_ACCUM_TU defined: that translation unit holds the ACC
+// instantiations of the kernels (through launch_accum) and none of the other entry points, so the code
+// object of this one -- every one-shot kernel -- is built from exactly what it was built from without them
+#ifndef RT_ACCUM_TU
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fn, x, y, out, n);
@@ -1090,20 +1135,22 @@ hipError_t launch_debug_trace(const DevScene& sc, int traversal, const float* ra
     return hipGetLastError();
 }
 
-template <bool COUNT, bool STEP>
+#endif  // !RT_ACCUM_TU
+
+template <bool COUNT, bool STEP, bool ACC>
 hipError_t launch_resume(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
                          unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, bool smem, bool ovf) {
     if (smem)
-        return launch_t<TRAV_FAST, COUNT, false, true, true, false, false, STEP>(sc, fp, block, d_out, d_counts,
+        return launch_t<TRAV_FAST, COUNT, false, true, true, false, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts,
                                                                                  d_work, stream);
     if (ovf)
-        return launch_t<TRAV_FAST, COUNT, false, false, true, true, false, STEP>(sc, fp, block, d_out, d_counts,
+        return launch_t<TRAV_FAST, COUNT, false, false, true, true, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts,
                                                                                  d_work, stream);
-    return launch_t<TRAV_FAST, COUNT, false, false, true, false, false, STEP>(sc, fp, block, d_out, d_counts, d_work,
+    return launch_t<TRAV_FAST, COUNT, false, false, true, false, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts, d_work,
                                                                               stream);
 }
 
-template <bool COUNT>
+template <bool COUNT, bool ACC = false>
 hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
                        unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
     const size_t scene_bytes = (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
@@ -1119,35 +1166,36 @@ hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, flo
         const float cmax = std::max(std::fabs(fp.cam[0]), std::max(std::fabs(fp.cam[1]), std::fabs(fp.cam[2])));
         const bool dq = fp.wdq != 0 && sc.wdq_omax > 0.0f && cmax <= sc.wdq_omax;
         if (ovf)
-            return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, false, 1>(
+            return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, false, 1, ACC>(
                                sc, fp, block, d_out, d_counts, d_work, stream)
-                   : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 2>(
+                   : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 2, ACC>(
                                sc, fp, block, d_out, d_counts, d_work, stream)
-                         : launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 1>(
+                         : launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 1, ACC>(
                                sc, fp, block, d_out, d_counts, d_work, stream);
-        return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, false, 1>(
+        return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, false, 1, ACC>(
                            sc, fp, block, d_out, d_counts, d_work, stream)
-               : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 2>(
+               : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 2, ACC>(
                            sc, fp, block, d_out, d_counts, d_work, stream)
-                     : launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 1>(
+                     : launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 1, ACC>(
                            sc, fp, block, d_out, d_counts, d_work, stream);
     }
     if (resume) {
-        return step ? launch_resume<COUNT, true>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf)
-                    : launch_resume<COUNT, false>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf);
+        return step ? launch_resume<COUNT, true, ACC>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf)
+                    : launch_resume<COUNT, false, ACC>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf);
     }
     // BRUTE stages the scene in LDS: only while two blocks still fit a CU
     const size_t brute_lds = (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 +
                              (size_t)sc.nbox * 32 + (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF);
     if (sc.ntri > 0 && sc.nbrute > 0 && brute_lds <= 80 * 1024)
-        return launch_t<TRAV_FAST, COUNT, false, false, false, false, true>(sc, fp, block, d_out, d_counts, d_work,
+        return launch_t<TRAV_FAST, COUNT, false, false, false, false, true, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work,
                                                                             stream);
-    if (smem) return launch_t<TRAV_FAST, COUNT, false, true>(sc, fp, block, d_out, d_counts, d_work, stream);
+    if (smem) return launch_t<TRAV_FAST, COUNT, false, true, false, false, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
     if (ovf)
-        return launch_t<TRAV_FAST, COUNT, false, false, false, true>(sc, fp, block, d_out, d_counts, d_work, stream);
-    return launch_t<TRAV_FAST, COUNT, false>(sc, fp, block, d_out, d_counts, d_work, stream);
+        return launch_t<TRAV_FAST, COUNT, false, false, false, true, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
+    return launch_t<TRAV_FAST, COUNT, false, false, false, false, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
 }
 
+#ifndef RT_ACCUM_TU
 // ---- two-pass ordering (FrameParams::pass): pilot costs -> pixel order, most expensive first ----
 // Pixels are ordered in chunks of `chunk` consecutive tile pixels: the chunks by their summed pilot
 // cost, the pixels of a chunk in tile order.  The tree walk orders single pixels (its lanes diverge
@@ -1364,6 +1412,42 @@ hipError_t launch_render_pass(const DevScene& sc, const FrameParams& fp, int tra
                     : launch_fast<false>(sc, fp, block, d_out, d_counts, d_work, stream);
 }
 
+#endif  // !RT_ACCUM_TU
+
+#ifdef RT_ACCUM_TU
+// One add of a progressive accumulation: the ACC instantiation of the one-pass kernel launch_render_pass picks
+hipError_t launch_accum(const DevScene& sc, const FrameParams& f0, float4* state, int base, int traversal, int block,
+                        float* d_out, unsigned int* d_work, hipStream_t stream) {
+    if (!state || base < 0 || f0.spp <= base || f0.pass != 0 || f0.pilot != 0) return hipErrorInvalidValue;
+    FrameParams fp = f0;
+    fp.pilot_state = state;
+    fp.pilot = base;
+    if (traversal == TRAV_REF)
+        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, true>(sc, fp, block, d_out, nullptr,
+                                                                                          d_work, stream);
+    return launch_fast<false, true>(sc, fp, block, d_out, nullptr, d_work, stream);
+}
+
+#endif  // RT_ACCUM_TU
+
+#ifndef RT_ACCUM_TU
+// rt_accum_read: the frame of an accumulation state, clamp(acc / s) as store_pixel writes it
+__global__ void accum_resolve_kernel(const float4* __restrict__ state, float* __restrict__ out, int64_t n) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const float4 a = state[2 * p], b = state[2 * p + 1];
+    const rtm_f3 o = rtm_div(rtm_v3(a.x, a.y, a.z), (float)__float_as_int(b.w));
+    out[3 * p + 0] = rtm_fmax(rtm_fmin(o.x, 1.0f), 0.0f);
+    out[3 * p + 1] = rtm_fmax(rtm_fmin(o.y, 1.0f), 0.0f);
+    out[3 * p + 2] = rtm_fmax(rtm_fmin(o.z, 1.0f), 0.0f);
+}
+
+hipError_t launch_accum_resolve(const float4* state, float* d_out, int64_t n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, state, d_out, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_rgb8(const float* d_in, uint8_t* d_out, int64_t n, bool gamma, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     // float4 loads and 32-bit stores need 16- and 4-byte alignment (torch / hipMalloc buffers have it)
@@ -1384,5 +1468,7 @@ hipError_t launch_gamma(const float* d_in, float* d_out, int64_t n, hipStream_t 
     hipLaunchKernelGGL(gamma_kernel, dim3((unsigned)grid), dim3(block), 0, stream, d_in, d_out, n);
     return hipGetLastError();
 }
+
+#endif  // !RT_ACCUM_TU
 
 }  // namespace rt

@@ -2,7 +2,7 @@
  * include/rt_scene.h) with no Python and no torch: what a non-Python host of the reference's
  * device path would do in place of KernelLauncher (KernelLauncher.py:8-103).
  *
- *   render_scene SCENE.obj PARAMS.bin OUT_PREFIX
+ *   render_scene SCENE.obj PARAMS.bin OUT_PREFIX [ADDS]
  *
  * SCENE.obj is parsed by the native importer (rt_obj_parse: FileManager.py:253-304 semantics) and
  * its BVH built by the native BVH.py builder (rt_bvh_build, bit-identical export).  The .ini side of
@@ -13,7 +13,9 @@
  * The program checks the scene on the host (rt_scene_check), renders it (rt_render, the
  * launch_Raytracing semantics), quantises it (rt_render_rgb8, FileManager.saveImg) and applies the
  * gamma kernel (rt_gamma, ImgProcessing.cl), and writes OUT_PREFIX.f32 (float32 RGB),
- * OUT_PREFIX.rgb8 and OUT_PREFIX.gamma.f32.  Exit status 0 on success. */
+ * OUT_PREFIX.rgb8 and OUT_PREFIX.gamma.f32.  With ADDS (1 <= ADDS <= spp) the frame is rendered
+ * progressively instead: the spp samples in ADDS calls of rt_accum_add (and of rt_accum_add_rgb8 for the
+ * 8-bit frame) on one accumulation each -- the files are the same bytes.  Exit status 0 on success. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,10 +59,11 @@ static int take(reader* r, void* dst, long bytes) {
 #define FAIL(...) do { fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); goto done; } while (0)
 
 int main(int argc, char** argv) {
-    if (argc != 4) {
-        fprintf(stderr, "usage: %s SCENE.obj PARAMS.bin OUT_PREFIX\n", argv[0]);
+    if (argc != 4 && argc != 5) {
+        fprintf(stderr, "usage: %s SCENE.obj PARAMS.bin OUT_PREFIX [ADDS]\n", argv[0]);
         return 2;
     }
+    const int adds = argc == 5 ? atoi(argv[4]) : 0;   /* 0: one-shot rt_render */
     int rc = 1;
     rt_obj* obj = NULL;
     rt_ctx* ctx = NULL;
@@ -123,9 +126,28 @@ int main(int argc, char** argv) {
     gam = (float*)malloc(sizeof(float) * 3 * (size_t)npix);
     out8 = (uint8_t*)malloc(3 * (size_t)npix);
     if (!out || !gam || !out8) FAIL("out of memory");
-    if (rt_render(ctx, cam, env, npix, spp, max_bounce, out) != RT_OK) FAIL("rt_render: %s", rt_last_error(ctx));
-    if (rt_render_rgb8(ctx, cam, env, npix, spp, max_bounce, 0, out8) != RT_OK)
-        FAIL("rt_render_rgb8: %s", rt_last_error(ctx));
+    if (argc == 5) {
+        /* progressive: the frame after every add is a finished frame at the samples done so far (a viewer
+         * would show each); the last one is the one-shot frame */
+        if (adds < 1 || adds > spp) FAIL("ADDS must be in 1..spp");
+        for (int pass = 0; pass < 2; ++pass) {
+            if (rt_accum_begin(ctx, cam, env, npix, max_bounce) != RT_OK) FAIL("rt_accum_begin: %s", rt_last_error(ctx));
+            for (int k = 0; k < adds; ++k) {
+                const int n = spp / adds + (k < spp % adds ? 1 : 0);
+                const int st = pass == 0 ? rt_accum_add(ctx, n, out) : rt_accum_add_rgb8(ctx, n, 0, out8);
+                if (st != RT_OK) FAIL("rt_accum_add: %s", rt_last_error(ctx));
+            }
+            if (rt_accum_samples(ctx) != spp) FAIL("rt_accum_samples: %lld", (long long)rt_accum_samples(ctx));
+        }
+        if (rt_accum_read(ctx, gam) != RT_OK) FAIL("rt_accum_read: %s", rt_last_error(ctx));
+        if (memcmp(gam, out, sizeof(float) * 3 * (size_t)npix) != 0) FAIL("rt_accum_read differs from the last add");
+        if (rt_accum_end(ctx) != RT_OK) FAIL("rt_accum_end: %s", rt_last_error(ctx));
+        printf("accumulated in %d adds\n", adds);
+    } else {
+        if (rt_render(ctx, cam, env, npix, spp, max_bounce, out) != RT_OK) FAIL("rt_render: %s", rt_last_error(ctx));
+        if (rt_render_rgb8(ctx, cam, env, npix, spp, max_bounce, 0, out8) != RT_OK)
+            FAIL("rt_render_rgb8: %s", rt_last_error(ctx));
+    }
     if (rt_gamma(ctx, out, gam, 3 * (int64_t)npix) != RT_OK) FAIL("rt_gamma: %s", rt_last_error(ctx));
     /* a call the boundary must refuse, and say why */
     if (rt_set_option(ctx, "no_such_option", 1) == RT_OK) FAIL("an unknown option was accepted");

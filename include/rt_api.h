@@ -110,6 +110,52 @@ int rt_render_device(rt_ctx* ctx, int device_index, const float cam[10], const f
 /* Number of rows rt_render_device writes for (npix, W, row0, row_step). */
 int64_t rt_tile_rows(int64_t npix, int width, int row0, int row_step);
 
+/* Progressive rendering: accumulate the samples of one frame over several calls.  The reference sums a
+ * pixel's samples in order over one RNG chain, divides by the count and clamps (Raytracing.cl:191-220), so
+ * adds of a and then b samples give, bit for bit, the frame of a one-shot render at a + b samples.
+ *
+ * A context holds at most one accumulation.  Its per-pixel state (sum, RNG words, the cached camera hit as
+ * reference triangle index and distance, samples done: 32 bytes per pixel) lives in a device buffer of its
+ * own per device slot: rt_render*, rt_count_work* and the debug entry points may be called between two adds.
+ *   rt_accum_begin     open an accumulation of the frame (cam, env, npix, max_bounce as rt_render; the same
+ *                      argument checks), no samples yet; replaces an open one.
+ *   rt_accum_add       run spp >= 1 more samples of every pixel, blocking; out_rgb[3*npix] (may be NULL)
+ *                      receives clamp(sum / total) exactly as rt_render at the total would write it.  Rows
+ *                      are split over the device slots as in rt_render.
+ *   rt_accum_add_rgb8  the same, the frame quantised on the device(s) as rt_render_rgb8 does (a preview).
+ *   rt_accum_read      the frame at the samples done; nothing is rendered.
+ *   rt_accum_samples   samples done per pixel; -1 when no accumulation is open (NULL context: -1).
+ *   rt_accum_end       free the state (no error when none is open).
+ * Limit: the total may not exceed RT_ACCUM_MAX_SAMPLES (2^24: the sample count stays exact as a float
+ * divisor and the sample-slice arithmetic of an add within 32 bits); an add past it, or spp < 1, is
+ * RT_ERR_ARG and adds nothing.
+ * RT_ERR_STATE: add or read with no accumulation open, read before the first add, and add or read after the
+ * accumulation was invalidated.  rt_set_scene, rt_set_env and rt_set_option of "traversal" or "ref_stack"
+ * invalidate it (rt_accum_samples stays readable; begin again or end it).  Every other option keeps it
+ * valid -- "bvh", "brute_max" and "bvh_width" included: they give the same hits, and the state is
+ * engine-neutral.  Scheduling: an add is always one pass; it takes sample slices as a one-shot render
+ * would, over the samples it adds, and never a pilot pass or speculative trails ("pilot" and "spec" do not
+ * apply to it). */
+#define RT_ACCUM_MAX_SAMPLES (1 << 24)
+int rt_accum_begin(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int max_bounce);
+int rt_accum_add(rt_ctx* ctx, int spp, float* out_rgb);
+int rt_accum_add_rgb8(rt_ctx* ctx, int spp, int gamma, uint8_t* out_rgb8);
+int rt_accum_read(rt_ctx* ctx, float* out_rgb);
+int64_t rt_accum_samples(rt_ctx* ctx);
+int rt_accum_end(rt_ctx* ctx);
+/* Tile form, for the one-rank-per-GPU path: the state is per (context, device slot).
+ *   rt_accum_begin_device  open an accumulation of the rows row0, row0 + row_step, ... on slot device_index
+ *                          (replaces that slot's; rt_accum_begin is this call on every slot, row k of n).
+ *   rt_accum_add_device    enqueue spp more samples of the tile on the HIP stream `stream` (NULL = the
+ *                          default stream) into DEVICE memory d_out, packed as rt_render_device packs it.
+ * Asynchrony: rt_accum_add_device returns once the launch is enqueued, as rt_render_device does; unlike
+ * rt_render_device it never waits on the stream (it has no pilot pass whose result the host reads).  The
+ * state and d_out are complete when the work enqueued on `stream` is; adds on different streams are ordered
+ * by the context, as its renders are.  rt_accum_samples counts an add from the moment it is enqueued. */
+int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5],
+                          int64_t npix, int max_bounce, int row0, int row_step);
+int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),
