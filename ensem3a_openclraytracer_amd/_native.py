@@ -33,14 +33,14 @@ EXPORTED = (
     "rt_accum_begin", "rt_accum_add", "rt_accum_add_rgb8", "rt_accum_read", "rt_accum_samples", "rt_accum_end",
     "rt_accum_begin_device", "rt_accum_add_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
-    "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings",
+    "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
 # The host-only entry points (no GPU, no HIP call): the sanitizer build (oracle/Makefile asan,
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
-             "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis")
+             "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -123,6 +123,8 @@ def lib():
             "rt_obj_last_error": (ctypes.c_char_p, []),
             "rt_scene_check": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _c_p]),
             "rt_scene_last_error": (ctypes.c_char_p, []),
+            "rt_debug_brute_layout": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _c_p, _i64,
+                                             _c_p]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
@@ -442,6 +444,24 @@ def scene_check(V_p, V_n, faceData, materialData, bvh, layout: int = RT_BVH_SAH)
     return dict(tris=int(info[0]), nodes=int(info[1]), depth=int(info[2]), wnodes=int(info[3]),
                 wdepth=int(info[4]), brute_records=int(info[5]), brute_boxes=int(info[6]), fast_ok=bool(info[7]),
                 note=msg)
+
+
+def brute_layout(V_p, V_n, faceData, materialData, bvh, layout: int = RT_BVH_SAH):
+    """rt_debug_brute_layout (include/rt_debug.h): the brute-force box array rt_set_scene would upload,
+    on the host alone.  Returns ``(slots, nbox, nbrute)``: slots is a float32 array of 8 floats per slot,
+    padding slots included (columns 6 and 7 hold the int bits of the slot's records)."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    H = host_lib()
+    info = np.zeros(3, np.int64)
+    args = (ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size, ptr(b), b.size, int(layout))
+    st = H.rt_debug_brute_layout(*args, None, 0, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    boxes = np.zeros(int(info[2]), np.float32)
+    st = H.rt_debug_brute_layout(*args, boxes.ctypes.data, boxes.size, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    return boxes.reshape(-1, 8), int(info[0]), int(info[1])
 
 
 def tile_rows(npix: int, width: int, row0: int, row_step: int) -> int:

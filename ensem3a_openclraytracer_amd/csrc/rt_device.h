@@ -516,7 +516,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
     };
     if (ts == 1) {
         // kBoxGroup distinct leaf boxes per scalar wait: the group is loaded together (2 float4 per box:
-        // the box and its one or two records; padded with never-hit boxes), all its slab tests run back
+        // the box and its one or two records; padded with boxes that list record 0), all its slab tests run back
         // to back, then the passes are queued (culling uses the best hit as of the group's start:
         // conservative)
         const ConstF4 cb = as_const(S.brute_box);
@@ -535,9 +535,11 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             }
 #pragma unroll
             for (int j = 0; j < kBoxGroup; ++j) {
-                // padding boxes (a point at 1e30: every slab distance is beyond the cull or behind the ray) never
-                // pass, so the product build queues nothing for them without a check (r06: the 1/8 tile 2.19 ->
-                // 2.16 ms, the frame unchanged); the instrumented build skips them so the counters stay exact
+                // padding boxes (a point at 1e30 listing record 0 alone, scene_pack.cpp pad_box) pass only for
+                // rays with a NaN component (slab() and box_hit() drop NaN) or from about 1e30 (1, 1, 1); the
+                // product build queues them without a check (r06: the 1/8 tile 2.19 -> 2.16 ms, the frame
+                // unchanged): such a pass tests record 0 once more for its owner, which cannot change the
+                // owner's minimum (k, rank) key.  The instrumented build skips them so the counters stay exact
                 if (COUNT && g0 + j >= S.nbox) break;
                 const int qa = __float_as_int(bx[2 * j + 1].z), qb = __float_as_int(bx[2 * j + 1].w);
                 if (COUNT) {   // counted per record (one leaf box test each, as in the tree walk)

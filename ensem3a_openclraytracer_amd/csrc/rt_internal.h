@@ -63,8 +63,11 @@ struct DevScene {
     const float4* brute;
     int32_t nbrute;
     // the distinct leaf boxes, 2 float4 each (lo.x hi.x lo.y hi.y | lo.z hi.z q0 q1): q0 (and q1 >= 0,
-    // int bits) are the records whose leaf box it is.  Padded to whole groups of kBoxGroup with boxes
-    // no ray reaches: the lock-step loop loads a group with one scalar wait
+    // int bits) are the records whose leaf box it is.  Padded to whole groups of kBoxGroup (the lock-step
+    // loop loads a group with one scalar wait) with a point at 1e30 that lists record 0 alone: a ray
+    // with a NaN component, or one from 1e30 (1, 1, 1), passes it (the slab test drops NaN), and then
+    // tests record 0 again, which changes no hit.  Every slot's q0 is a valid record and q1 is one or -1
+    // (scene_pack.cpp pad_box; tests/test_malformed_inputs.py checks every slot)
     const float4* brute_box;
     int32_t nbox;
 };

@@ -1150,12 +1150,21 @@ hipError_t launch_resume(const DevScene& sc, const FrameParams& fp, int block, f
                                                                               stream);
 }
 
+// A small tree-walk scene is staged in LDS (SMEM kernels).  Those kernels keep the whole stack in LDS too:
+// they have no spill code, and the staged arrays start right behind stack_lds entries per lane, so an
+// entry past stack_lds would overwrite the staged nodes.  Hence only trees no deeper than stack_lds: a
+// small but deep tree (a 40-level chain, or any tree with option "stack_lds" below its depth) walks the
+// arrays in global memory with the overflow buffer instead.
+static bool stage_in_lds(const DevScene& sc) {
+    const size_t scene_bytes = (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
+    return sc.ntri > 0 && sc.nbrute == 0 && scene_bytes <= kLdsSceneMax && sc.stack_lds >= sc.depth;
+}
+
 template <bool COUNT, bool ACC = false>
 hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
                        unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
-    const size_t scene_bytes = (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
-    const bool smem = sc.ntri > 0 && sc.nbrute == 0 && scene_bytes <= kLdsSceneMax;
     const bool ovf = sc.nbrute == 0 && sc.stack_lds < sc.depth;
+    const bool smem = stage_in_lds(sc);
     const bool resume = sc.ntri > 0 && sc.nbrute == 0 && fp.resume_min > 0;
     const bool step = fp.step == 1 || (fp.step == 0 && (size_t)sc.nnodes * kNodeF4 * 16 <= kStepMaxBytes);
     if (resume && fp.wide && sc.wnodes && !smem) {
@@ -1163,8 +1172,11 @@ hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, flo
         // the item steps dequantise origin-folded (WIDE 2) when every ray origin of the frame is within
         // the bound the builder's gap covers: hit points always are, the camera is checked here
         const bool step = fp.step != 2;
-        const float cmax = std::max(std::fabs(fp.cam[0]), std::max(std::fabs(fp.cam[1]), std::fabs(fp.cam[2])));
-        const bool dq = fp.wdq != 0 && sc.wdq_omax > 0.0f && cmax <= sc.wdq_omax;
+        // (each coordinate compared on its own: false for a NaN in any of them, which a std::max over the
+        // three would drop from its second operand)
+        const bool cam_in = std::fabs(fp.cam[0]) <= sc.wdq_omax && std::fabs(fp.cam[1]) <= sc.wdq_omax &&
+                            std::fabs(fp.cam[2]) <= sc.wdq_omax;
+        const bool dq = fp.wdq != 0 && sc.wdq_omax > 0.0f && cam_in;
         if (ovf)
             return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, false, 1, ACC>(
                                sc, fp, block, d_out, d_counts, d_work, stream)
@@ -1395,8 +1407,7 @@ hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, fl
 // the launches whose FAST walk is the BVH2 item-step resumable kernel (launch_fast's choice), the walk
 // rt_spec.hip continues
 bool spec_walk(const DevScene& sc, const FrameParams& fp) {
-    const size_t scene_bytes = (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
-    const bool smem = sc.ntri > 0 && sc.nbrute == 0 && scene_bytes <= kLdsSceneMax;
+    const bool smem = stage_in_lds(sc);
     const bool resume = sc.ntri > 0 && sc.nbrute == 0 && fp.resume_min > 0;
     const bool step = fp.step == 1 || (fp.step == 0 && (size_t)sc.nnodes * kNodeF4 * 16 <= kStepMaxBytes);
     return resume && !smem && step && !(fp.wide && sc.wnodes);

@@ -52,6 +52,19 @@ inline bool fidx(float v, int64_t limit, int32_t* out) {
 // kernels dequantise it (rt_kernels.hip wide_step; this file is built with -ffp-contract=off).
 inline float deq(float p, uint32_t q, float s) { return p + (float)q * s; }
 
+// A padding slot of DevScene::brute_box (8 floats): a point at 1e30, which no finite ray near the
+// scene reaches within k < 1000, listing record 0 alone.  The product build of the brute-force loop
+// queues whatever a passing slot lists, and the slab test does pass here for some rays: fminf / fmaxf
+// drop NaN operands, so a ray with a NaN origin or direction passes every box, and so does a ray from
+// (1e30, 1e30, 1e30) (every slab distance 0).  Such a pass then tests record 0 once more for its owner,
+// which cannot change the owner's minimum (distance, rank) key.  Record 0 always exists: the record
+// array holds at least one (zero) record.
+inline void pad_box(float* b) {
+    for (int k = 0; k < 6; ++k) b[k] = 1e30f;
+    b[6] = as_f32(0);
+    b[7] = as_f32(-1);
+}
+
 
 // f(begin, end) over [0, n) in chunks of `grain`, on up to 16 host threads (the caller's included)
 template <class F>
@@ -471,8 +484,8 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
         // the distinct leaf boxes, 32 bytes each: records whose leaf boxes are bit-identical (the
         // two triangles of an axis-aligned or vertical quad) share one box test, which passes or
         // fails for both.  Each box lists up to two records (the second -1 when alone); padded with
-        // never-hit boxes to whole groups of rt::kBoxGroup (the lock-step loop loads a group with
-        // one scalar wait).
+        // pad_box() to whole groups of rt::kBoxGroup (the lock-step loop loads a group with one
+        // scalar wait).
         std::vector<std::array<int32_t, 2>> groups;
         {
             std::map<std::array<uint32_t, 6>, size_t> open;   // box bits -> group with a free slot
@@ -502,8 +515,7 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
                 b[4] = r[2]; b[5] = r[5];                                // lo.z hi.z
                 b[6] = as_f32(groups[g][0]); b[7] = as_f32(groups[g][1]);
             } else {
-                for (int k = 0; k < 6; ++k) b[k] = 1e30f;                // a point far beyond any k < 1000
-                b[6] = as_f32(-1); b[7] = as_f32(-1);
+                pad_box(b);
             }
         }
     }
@@ -566,7 +578,10 @@ void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, in
     }
     if (hs.nodes.empty()) hs.nodes.assign(4 * rt::kNodeF4, 0.0f);
     if (hs.brute.empty()) hs.brute.assign(16, 0.0f);
-    if (hs.brute_box.empty()) hs.brute_box.assign(8 * rt::kBoxGroup, 1e30f);
+    if (hs.brute_box.empty()) {   // never read (nbox = 0): one group of padding slots, ids valid all the same
+        hs.brute_box.assign(8 * rt::kBoxGroup, 0.0f);
+        for (int g = 0; g < rt::kBoxGroup; ++g) pad_box(hs.brute_box.data() + 8 * g);
+    }
 }
 
 namespace {
@@ -703,3 +718,28 @@ extern "C" int rt_scene_check(const float* vp, int64_t nvp, const float* vn, int
 }
 
 extern "C" const char* rt_scene_last_error(void) { return g_check_error.c_str(); }
+
+extern "C" int rt_debug_brute_layout(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                     int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                     int layout, float* boxes, int64_t cap, int64_t info[3]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (!info || cap < 0 || (cap > 0 && !boxes)) {
+        g_check_error = "null info, or a box capacity without an array";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[0] = hs.nbox;
+    info[1] = hs.nbrute;
+    info[2] = (int64_t)hs.brute_box.size();
+    const int64_t n = std::min<int64_t>(cap, info[2]);
+    if (n > 0) std::memcpy(boxes, hs.brute_box.data(), (size_t)n * sizeof(float));
+    return RT_OK;
+}

@@ -79,6 +79,18 @@ int rt_debug_timings(rt_ctx* ctx, double out[4]);
  * BVH2 walk (gap = 0) or quantises without the gap (emit_wide). */
 int rt_debug_quantise_axis(float p, const float* lo, const float* hi, int n, float gap, uint8_t* qlo, uint8_t* qhi);
 
+/* Host-only (no device): the brute-force box array rt_set_scene would upload for these arrays (the
+ * arrays, layout and statuses of rt_scene_check in rt_scene.h; errors through rt_scene_last_error).
+ * info[0] = distinct leaf boxes, info[1] = brute-force records (0: the scene renders through the tree
+ * walk and the array is one group of padding slots), info[2] = floats in the array: 8 per slot (lo.x
+ * hi.x lo.y hi.y lo.z hi.z, then the int bits of the slot's first record and of its second or -1),
+ * padding slots up to a whole group of 4 included.  The first min(cap, info[2]) floats are copied to
+ * boxes (boxes may be NULL when cap is 0).  The kernels queue the records of every slot that a ray's
+ * slab test passes, padding included, so every slot must list valid records. */
+int rt_debug_brute_layout(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                          int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                          int layout, float* boxes, int64_t cap, int64_t info[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,3 +194,93 @@ def test_scene_check_empty_scene():
     info = _native.scene_check(np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32),
                                np.array([1, 1, 1, 1, 0, 0], np.float32), np.zeros(0, np.float32))
     assert info["tris"] == 0
+
+
+# ---- the brute-force box array (rt_debug_brute_layout): every slot a passing ray can queue is valid ----
+
+# Cornell (22 distinct boxes) and seeded soups; nbox % 4 != 0 on at least four, so padding slots exist
+BRUTE_SCENES = ["cornell", (6, 1), (7, 2), (20, 5), (0, 7), (9, 33), (2, 64)]
+
+
+def _brute_scene(which):
+    if which == "cornell":
+        return _cornell()
+    from tests.test_gpu_parity import _random_scene
+    return _random_scene(*which)
+
+
+def _brute_layout(which):
+    sc = _brute_scene(which)
+    slots, nbox, nbrute = _native.brute_layout(sc.V_p, sc.V_n, sc.faceData, sc.materialData, sc.BVH.exportArray)
+    return sc, slots, nbox, nbrute
+
+
+def test_brute_layout_scenes_have_padding_slots():
+    rem = []
+    for which in BRUTE_SCENES:
+        sc, slots, nbox, nbrute = _brute_layout(which)
+        assert nbrute == sc.faceData.size // 10 and 0 < nbox <= nbrute
+        assert len(slots) == -(-nbox // 4) * 4            # whole groups of rt_layout.h kBoxGroup
+        rem.append(nbox % 4)
+    assert sum(r != 0 for r in rem) >= 4, rem
+    assert _brute_layout("cornell")[2] == 22              # C2: two padding slots
+
+
+@pytest.mark.parametrize("which", BRUTE_SCENES, ids=str)
+def test_brute_layout_every_slot_names_valid_records(which):
+    """The product build of the brute-force loop queues the records of every slot whose slab test passes,
+    padding slots included (rt_device.h trace_brute_compact), and run_batch indexes the record array, the
+    LDS ray table and the best-key table with what the slot holds: qa must be a record, qb a record or -1."""
+    sc, slots, nbox, nbrute = _brute_layout(which)
+    ids = slots[:, 6:8].copy().view(np.int32)
+    qa, qb = ids[:, 0], ids[:, 1]
+    assert ((qa >= 0) & (qa < nbrute)).all(), qa
+    assert ((qb == -1) | ((qb >= 0) & (qb < nbrute))).all(), qb
+    # the real slots list every record exactly once
+    real = np.concatenate([qa[:nbox], qb[:nbox][qb[:nbox] >= 0]])
+    assert sorted(real.tolist()) == list(range(nbrute))
+    # padding: the point at 1e30, listing record 0 alone
+    assert (slots[nbox:, :6] == np.float32(1e30)).all() and (qa[nbox:] == 0).all() and (qb[nbox:] == -1).all()
+
+
+@pytest.mark.parametrize("which", BRUTE_SCENES, ids=str)
+def test_brute_layout_rays_that_pass_padding_slots(which):
+    """A numpy restatement of slab() + box_hit() over the non-finite ray classes: padding slots do pass
+    (NaN rays pass every box, a ray from 1e30 (1, 1, 1) passes the point at 1e30), so "padding never
+    passes" was never true; whatever passes must name valid records."""
+    from tests import nonfinite_rays as NR
+    sc, slots, nbox, nbrute = _brute_layout(which)
+    leaf = sc.BVH.exportArray.reshape(-1, 9)
+    leaf = leaf[leaf[:, 8] >= 0][:, 2:8]
+    classes = NR.ray_classes([0.0, -3.5, 0.0], leaf, seed=1)
+    ids = slots[:, 6:8].copy().view(np.int32)
+    passed_padding = {}
+    for name, rays in classes.items():
+        p = NR.slab_pass(slots[:, :6], rays)                 # (rays, slots)
+        q = ids[np.nonzero(p)[1]]
+        assert ((q[:, 0] >= 0) & (q[:, 0] < nbrute)).all(), name
+        assert ((q[:, 1] == -1) | ((q[:, 1] >= 0) & (q[:, 1] < nbrute))).all(), name
+        passed_padding[name] = bool(p[:, nbox:].any())
+    assert not passed_padding["finite"]
+    if len(slots) > nbox:
+        assert passed_padding["nan_all"] and passed_padding["nan_origin_all"] and passed_padding["nan_dir_all"]
+        assert passed_padding["far_origin_1e30"]
+        # every ray of these classes passes every slot: the worst case of the pair queue
+        for name in ("nan_all", "nan_origin_all", "nan_dir_all"):
+            assert NR.slab_pass(slots[:, :6], classes[name]).all(), name
+
+
+def test_brute_layout_of_a_tree_walk_scene_and_of_no_scene():
+    """Scenes the tree walk renders (more than 64 triangles) and the empty scene upload one group of
+    padding slots that no kernel reads (nbox = 0); its ids are record 0 / -1 like any padding."""
+    from tests.test_gpu_parity import _random_scene
+    sc = _random_scene(8, 65)
+    for args in ((sc.V_p, sc.V_n, sc.faceData, sc.materialData, sc.BVH.exportArray),
+                 (np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32),
+                  np.array([1, 1, 1, 1, 0, 0], np.float32), np.zeros(0, np.float32))):
+        slots, nbox, nbrute = _native.brute_layout(*args)
+        assert (nbox, nbrute, len(slots)) == (0, 0, 4)
+        ids = slots[:, 6:8].copy().view(np.int32)
+        assert (ids[:, 0] == 0).all() and (ids[:, 1] == -1).all() and (slots[:, :6] == np.float32(1e30)).all()
+    with pytest.raises(_native.NativeError):
+        _native.brute_layout(sc.V_p[:-1], sc.V_n, sc.faceData, sc.materialData, sc.BVH.exportArray)
