@@ -34,13 +34,15 @@ EXPORTED = (
     "rt_accum_begin_device", "rt_accum_add_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
+    "rt_debug_brute_clusters",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
 # The host-only entry points (no GPU, no HIP call): the sanitizer build (oracle/Makefile asan,
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
-             "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout")
+             "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout",
+             "rt_debug_brute_clusters")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -125,6 +127,8 @@ def lib():
             "rt_scene_last_error": (ctypes.c_char_p, []),
             "rt_debug_brute_layout": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _c_p, _i64,
                                              _c_p]),
+            "rt_debug_brute_clusters": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32,
+                                               _c_p, _i64, _c_p, _i64, _c_p]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
@@ -462,6 +466,26 @@ def brute_layout(V_p, V_n, faceData, materialData, bvh, layout: int = RT_BVH_SAH
     if st != 0:
         raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
     return boxes.reshape(-1, 8), int(info[0]), int(info[1])
+
+
+def brute_clusters(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, layout: int = RT_BVH_SAH):
+    """rt_debug_brute_clusters (include/rt_debug.h): the clustered box array option "brute_cluster" = cluster
+    uploads, on the host alone.  Returns ``(slots, rows, nsingle)``: slots as brute_layout's (the singles
+    padded to a group of 4, then 8 slots per cluster), rows 8 floats per cluster (the union box, then the int
+    bits of first slot and box count); both empty when the scene is not clustered."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    H = host_lib()
+    info = np.zeros(4, np.int64)
+    args = (ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size, ptr(b), b.size, int(layout),
+            int(cluster))
+    st = H.rt_debug_brute_clusters(*args, None, 0, None, 0, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    slots, rows = np.zeros(int(info[2]), np.float32), np.zeros(int(info[3]), np.float32)
+    st = H.rt_debug_brute_clusters(*args, slots.ctypes.data, slots.size, rows.ctypes.data, rows.size, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    return slots.reshape(-1, 8), rows.reshape(-1, 8), int(info[1])
 
 
 def tile_rows(npix: int, width: int, row0: int, row_step: int) -> int:

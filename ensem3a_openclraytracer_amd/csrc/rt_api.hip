@@ -48,7 +48,7 @@ struct Device {
     hipStream_t stream = nullptr;
     int cus = 0;                  // compute units (sizes the FAST stack overflow buffer)
     DevBuf stack_ovf;             // FAST traversal stack entries beyond the LDS part
-    DevBuf nodes, wnodes, wleaves, tri_fast, brute, brute_box, bvh9, tri_geo, tri_shade, tri_frame, mat, ibl, ibl_sum, out, out8, counts, work, scratch_a, scratch_b;
+    DevBuf nodes, wnodes, wleaves, tri_fast, brute, brute_box, brute_cbox, brute_crow, bvh9, tri_geo, tri_shade, tri_frame, mat, ibl, ibl_sum, out, out8, counts, work, scratch_a, scratch_b;
     DevBuf pilot;                 // two-pass launches: per-pixel state, cost and order (FrameParams::pilot_*)
     DevBuf spec;                  // speculation: the trails' sample logs (FrameParams::spec_log)
     DevBuf slice;                 // sample slices: per-pixel state + samples done (FrameParams::slice_*)
@@ -83,6 +83,7 @@ struct rt_ctx {
     int traversal = RT_TRAVERSAL_FAST;
     int bvh_layout = RT_BVH_SAH;
     int brute_max = RT_BRUTE_MAX_DEFAULT;
+    int brute_cluster = -1;  // brute force: clustered leaf boxes (0 off, 1 force, -1 auto; option "brute_cluster")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
     int walk_team = 0;  // tree walk (BVH2 item steps): lanes per pixel walking each ray together, 0 = auto
@@ -225,6 +226,12 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.brute_box = (const float4*)d.brute_box.p;
     s.nbrute = ctx->hs.nbrute;
     s.nbox = ctx->hs.nbox;
+    s.brute_cbox = (const float4*)d.brute_cbox.p;
+    s.brute_crow = (const float4*)d.brute_crow.p;
+    s.ncluster = ctx->hs.ncluster;
+    s.ncslot = (int32_t)(ctx->hs.brute_cbox.size() / 8);
+    s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
+    s.cluster_auto = ctx->brute_cluster < 0 ? 1 : 0;
     s.stack_lds = std::min<int32_t>(s.depth > 0 ? s.depth : 1,
                                     ctx->stack_lds > 0 ? ctx->stack_lds : wide ? rt::kStackLdsWide : rt::kStackLds);
     s.stack_ovf = (int2*)d.stack_ovf.p;
@@ -341,7 +348,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (hipSetDevice(d.id) != hipSuccess) continue;
         if (d.pending) (void)hipEventSynchronize(d.done);
         if (d.stream) (void)hipStreamSynchronize(d.stream);
-        for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
+        for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.brute_cbox, &d.brute_crow, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
                           &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum})
             release(*b);
         if (d.host_stage) (void)hipHostFree(d.host_stage);
@@ -363,11 +370,15 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         invalidate_accum(ctx);
         return RT_OK;
     }
-    if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max")) {
+    if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max") || !std::strcmp(key, "brute_cluster")) {
         if (!std::strcmp(key, "bvh")) {
             if (value != RT_BVH_REFERENCE && value != RT_BVH_SAH)
                 return set_err(ctx, RT_ERR_ARG, "bvh must be 0 (reference tree) or 1 (sah)");
             ctx->bvh_layout = (int)value;
+        } else if (!std::strcmp(key, "brute_cluster")) {
+            if (value < -1 || value > 1)
+                return set_err(ctx, RT_ERR_ARG, "brute_cluster must be -1 (auto), 0 (off) or 1 (force)");
+            ctx->brute_cluster = (int)value;
         } else {
             if (value < 0 || value > 4096) return set_err(ctx, RT_ERR_ARG, "brute_max must be in 0..4096");
             ctx->brute_max = (int)value;
@@ -375,7 +386,7 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         if (!ctx->have_scene) return RT_OK;
         HostScene& hs = ctx->hs;   // repack the FAST nodes of the current scene
         std::string why;
-        rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, why);
+        rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster, why);
         for (auto& d : ctx->devs) {
             HIP_OR_RET(ctx, hipSetDevice(d.id));
             HIP_OR_RET(ctx, order_after_last(d, d.stream));
@@ -386,6 +397,8 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
             HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
             HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
             HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
+            HIP_OR_RET(ctx, upload(d.brute_cbox, hs.brute_cbox, d.stream));
+            HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
             HIP_OR_RET(ctx, upload(d.tri_geo, hs.tri_geo, d.stream));
             HIP_OR_RET(ctx, upload(d.tri_fast, hs.tri_fast, d.stream));
             HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
@@ -512,7 +525,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     HostScene hs;
     std::string msg, why;
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, ctx->bvh_layout,
-                                     ctx->brute_max, msg, why);
+                                     ctx->brute_max, ctx->brute_cluster, msg, why);
     if (rc != RT_OK) return set_err(ctx, rc, "%s", msg.c_str());
     invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
@@ -526,6 +539,8 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
         HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
         HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
         HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
+        HIP_OR_RET(ctx, upload(d.brute_cbox, hs.brute_cbox, d.stream));
+        HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
         HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
         HIP_OR_RET(ctx, upload(d.bvh9, hs.bvh9, d.stream));
         HIP_OR_RET(ctx, upload(d.tri_geo, hs.tri_geo, d.stream));

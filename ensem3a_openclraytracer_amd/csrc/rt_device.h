@@ -427,7 +427,12 @@ __device__ __forceinline__ float4 sgpr4(float4 v) {
 // the minimum key is the reference's hit (lowest rank on equal distances).
 // Culling uses the owner's best as of the last batch (a conservative bound).
 constexpr unsigned BRUTE_RING = 256u;
-constexpr int BRUTE_WAVE_LDS = 64 * 6 * 4 + 64 * 8 + (BRUTE_RING + 64) * 4;   // ray table | best keys | pair ring + dummy slots
+constexpr unsigned BRUTE_OWNERS = 128u;   // owner list of the clustered loop (entries; a power of two)
+constexpr int BRUTE_INV_OFF = 64 * 6 * 4 + 64 * 8 + (BRUTE_RING + 64) * 4;
+// ray table | best keys | pair ring + dummy slots | clustered loop: inverse directions [3][64] | owner list
+constexpr int BRUTE_WAVE_LDS = BRUTE_INV_OFF + 64 * 3 * 4 + BRUTE_OWNERS * 4;
+// at most 64 owners join fewer than 64 / kClusterSlots + 2 waiting ones; an owner entry keeps its first slot above bit 8
+static_assert(kClusterLockNum >= 0 && kClusterLockNum <= 8 && BRUTE_OWNERS >= 64 + 64 / kClusterSlots + 2, "owner list");
 
 // Lanes of one wave hand data to each other through LDS here.  The hardware runs a
 // wave's LDS instructions in order; this keeps the compiler from reordering them
@@ -448,7 +453,20 @@ __device__ __forceinline__ void wave_lds_sync() {
 // the ts lanes of a team carry the same path (identical arithmetic), split the box tests between
 // them (lane `sub` of the team tests records sub, sub + ts, ...; records read from the LDS copy
 // at boxrec, 1 float4 per triangle, and mtrec) and share one owner slot (the team's first lane).
-template <bool COUNT>
+//
+// Clusters (CLU: the one-lane product kernels, on scenes with DevScene::ncluster > 0): boxes that few rays
+// reach -- C2's two blocks: 16 of 22 boxes, passed by 6 % of the bounce rays -- are not tested lock-step.
+// The wave tests each cluster's union box lock-step (a ray that passes a member passes the union: slab()
+// is monotone in the bounds, with the same cull).  When more than kClusterLockNum / 8 of the tracing lanes
+// pass, the cluster's slots run lock-step like single boxes.  Otherwise the passing lanes are appended to
+// a per-wave owner list (owner lane | first slot << 8), and whenever the list holds a wave of (owner,
+// slot) items -- kClusterSlots per entry, item i = entry i >> kClusterShift, slot i & 7 of it -- each lane
+// takes one: the owner's ray and inverse direction from the LDS tables, the slot from the LDS copy of
+// brute_cbox (boxrec), the same slab() / box_hit() with the owner's best hit so far as the cull (read from
+// bestk: never behind the owner's own bk), and queues the slot's records for the owner like a lock-step pass.
+// The tests a ray's boxes get, and the triangles it is tested against, are those of the lock-step loop up
+// to culling, which changes no hit.
+template <bool COUNT, bool CLU = false>
 __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* wl, const float4* mtrec,
                                    unsigned mtstride, Cnt& c, int ts = 1, const float4* boxrec = nullptr) {
     const unsigned lane = threadIdx.x & 63;
@@ -514,13 +532,12 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             bk = __uint_as_float((unsigned)(bestk[tl] >> 32));
         }
     };
-    if (ts == 1) {
-        // kBoxGroup distinct leaf boxes per scalar wait: the group is loaded together (2 float4 per box:
-        // the box and its one or two records; padded with boxes that list record 0), all its slab tests run back
-        // to back, then the passes are queued (culling uses the best hit as of the group's start:
-        // conservative)
-        const ConstF4 cb = as_const(S.brute_box);
-        for (int g0 = 0; g0 < S.nbox; g0 += kBoxGroup) {
+    // kBoxGroup distinct leaf boxes per scalar wait: the group is loaded together (2 float4 per box:
+    // the box and its one or two records; padded with boxes that list record 0), all its slab tests run back
+    // to back, then the passes are queued (culling uses the best hit as of the group's start:
+    // conservative).  Slots [gb, ge) of cb; nreal: the real slots of the array (instrumented build)
+    auto lockstep = [&](const ConstF4 cb, int gb, int ge, int nreal) __attribute__((always_inline)) {
+        for (int g0 = gb; g0 < ge; g0 += kBoxGroup) {
             float4 bx[2 * kBoxGroup];
 #pragma unroll
             for (int j = 0; j < 2 * kBoxGroup; ++j) bx[j] = sgpr4(cb[2 * g0 + j]);
@@ -540,7 +557,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 // product build queues them without a check (r06: the 1/8 tile 2.19 -> 2.16 ms, the frame
                 // unchanged): such a pass tests record 0 once more for its owner, which cannot change the
                 // owner's minimum (k, rank) key.  The instrumented build skips them so the counters stay exact
-                if (COUNT && g0 + j >= S.nbox) break;
+                if (COUNT && g0 + j >= nreal) break;
                 const int qa = __float_as_int(bx[2 * j + 1].z), qb = __float_as_int(bx[2 * j + 1].w);
                 if (COUNT) {   // counted per record (one leaf box test each, as in the tree walk)
                     c.boxes++;
@@ -550,6 +567,74 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 enqueue(pass[j], (unsigned)qa, qb);
             }
         }
+    };
+    // (CLU kernels are launched for clustered scenes only, launch_t: they carry no loop over brute_box)
+    if (CLU) {
+        float* inv = reinterpret_cast<float*>(wl + BRUTE_INV_OFF);                          // [3][64]
+        unsigned* olist = reinterpret_cast<unsigned*>(wl + BRUTE_INV_OFF + 64 * 3 * 4);    // [BRUTE_OWNERS]
+        const unsigned* besthi = reinterpret_cast<const unsigned*>(bestk) + 1;              // distance bits of bestk[i] at [2 i]
+        inv[lane] = ix; inv[64 + lane] = iy; inv[128 + lane] = iz;
+        const ConstF4 cb = as_const(S.brute_cbox);
+        lockstep(cb, 0, S.nsingle4, S.nsingle4);
+        unsigned ihead = 0, itail = 0;   // wave-uniform item positions; itail is a multiple of kClusterSlots
+        // one batch of n <= nact items: fewer than nact pairs are queued before it and it adds at most 2 n
+        auto run_items = [&](int n) __attribute__((always_inline)) {
+            bool pass = false;
+            unsigned ow = 0, qa = 0;
+            int qb = -1;
+            if (myrank < n) {
+                const unsigned i = ihead + (unsigned)myrank;
+                const unsigned e = olist[(i >> kClusterShift) & (BRUTE_OWNERS - 1)];
+                ow = e & 63u;
+                const unsigned slot = (e >> 8) + (i & (unsigned)(kClusterSlots - 1));
+                const rtm_f3 ro = rtm_v3(ray[ow], ray[64 + ow], ray[128 + ow]);
+                const float4 b0 = boxrec[2 * slot], b1 = boxrec[2 * slot + 1];
+                float tn, tx;
+                slab(b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, ro, inv[ow], inv[64 + ow], inv[128 + ow], tn, tx);
+                pass = box_hit(tn, tx, __uint_as_float(besthi[2 * ow]) * CULL_MARGIN);
+                qa = (unsigned)__float_as_int(b1.z);
+                qb = __float_as_int(b1.w);
+            }
+            ihead += (unsigned)n;
+            // the slot's first record, and its second where there is one, behind the first ones
+            const bool pass2 = pass && qb >= 0;
+            const unsigned long long m = __ballot(pass), m2 = __ballot(pass2);
+            if (m == 0) return;
+            const unsigned np = (unsigned)__popcll(m);
+            if (pass) ring[lane_prefix(m, tail) & (BRUTE_RING - 1)] = (ow << 16) | qa;
+            if (pass2) ring[lane_prefix(m2, tail + np) & (BRUTE_RING - 1)] = (ow << 16) | (unsigned)qb;
+            tail += np + (unsigned)__popcll(m2);
+            wave_lds_sync();
+            if ((int)(tail - head) >= nact) {
+                do run_batch(nact); while ((int)(tail - head) >= nact);
+                bk = __uint_as_float((unsigned)(bestk[tl] >> 32));
+            }
+        };
+        const ConstF4 cr = as_const(S.brute_crow);
+        const int lock = (nact * kClusterLockNum) >> 3;
+        for (int cl = 0; cl < S.ncluster; ++cl) {
+            const float4 u0 = sgpr4(cr[2 * cl]), u1 = sgpr4(cr[2 * cl + 1]);
+            float tn, tx;
+            slab(u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, o, ix, iy, iz, tn, tx);
+            const bool pass = box_hit(tn, tx, bk * CULL_MARGIN);
+            const unsigned long long m = __ballot(pass);
+            if (m == 0) continue;
+            const int np = __popcll(m);
+            const int first = __float_as_int(u1.z);
+            if (np > lock) {
+                lockstep(cb, first, first + kClusterSlots, S.ncslot);
+                continue;
+            }
+            // np <= lock < nact owners join fewer than nact / kClusterSlots + 1 waiting ones: the list never
+            // holds more than 64 + 8 of its BRUTE_OWNERS entries
+            if (pass) olist[lane_prefix(m, itail >> kClusterShift) & (BRUTE_OWNERS - 1)] = lane | ((unsigned)first << 8);
+            itail += (unsigned)np << kClusterShift;
+            wave_lds_sync();
+            while ((int)(itail - ihead) >= nact) run_items(nact);
+        }
+        while (itail != ihead) run_items(min((int)(itail - ihead), nact));
+    } else if (ts == 1) {
+        lockstep(as_const(S.brute_box), 0, S.nbox, S.nbox);
     } else {
         // box g = gg * ts + sub of each round (LDS copy of brute_box at boxrec); its second record, when
         // there is one, differs between the lanes of the wave: queued by a second call
@@ -587,13 +672,13 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
 // mtrec/mtstride: where the brute-force MT batches read triangle records (float4 units).
 // BLDS: the caller staged the MT records in LDS at mtrec (3 float4 per triangle); otherwise they
 // are read from the global brute-force records.
-template <int TRAV, bool COUNT, bool SOA = false, bool OVF = false, bool BLDS = false>
+template <int TRAV, bool COUNT, bool SOA = false, bool OVF = false, bool BLDS = false, bool CLU = false>
 __device__ __forceinline__ Hit trace(const DevScene& S, const float4* nodes, const float4* tris, rtm_f3 o, rtm_f3 d,
                                      int* stk, int B, const LaneStack& st, Cnt& c, const float4* mtrec = nullptr,
                                      int ts = 1, const float4* boxrec = nullptr) {
     if (TRAV == TRAV_REF) return trace_ref<COUNT>(S, o, d, stk, B, c);
     if (S.nbrute > 0)
-        return trace_brute_compact<COUNT>(S, o, d, reinterpret_cast<char*>(stk - threadIdx.x) +
+        return trace_brute_compact<COUNT, CLU>(S, o, d, reinterpret_cast<char*>(stk - threadIdx.x) +
                                                         (threadIdx.x >> 6) * BRUTE_WAVE_LDS,
                                           BLDS ? mtrec : S.brute + 1, BLDS ? 3u : 4u, c, BLDS ? ts : 1, boxrec);
     return trace_fast<COUNT, SOA, OVF>(S, nodes, tris, o, d, st, c);

@@ -70,6 +70,16 @@ struct DevScene {
     // (scene_pack.cpp pad_box; tests/test_malformed_inputs.py checks every slot)
     const float4* brute_box;
     int32_t nbox;
+    // the same boxes clustered (scene_pack.cpp build_clusters, option "brute_cluster"; ncluster = 0: not
+    // clustered): brute_cbox = ncslot slots of brute_box's form, the single boxes padded to nsingle4 (whole
+    // groups of kBoxGroup), then kClusterSlots slots per cluster (padded; every padding slot lists record 0
+    // alone); brute_crow = 2 float4 per cluster: the union box lo.x hi.x lo.y hi.y | lo.z hi.z, first slot,
+    // box count (int bits).  The one-lane product kernels test a cluster's boxes only for the rays that pass
+    // its union (rt_device.h trace_brute_compact); the instrumented and team kernels read brute_box.
+    const float4* brute_cbox;
+    const float4* brute_crow;
+    int32_t ncluster, ncslot, nsingle4;
+    int32_t cluster_auto;   // option "brute_cluster" is -1: launch_t clusters only tiles of at least a pixel per resident lane
 };
 
 struct FrameParams {

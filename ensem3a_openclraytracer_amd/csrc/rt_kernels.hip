@@ -85,6 +85,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         for (int q = threadIdx.x; q < S.ntri; q += B) ls[q] = S.tri_shade[q];
         for (int q = threadIdx.x; q < 3 * S.ntri; q += B) lf[q] = S.tri_frame[q];
         for (int q = threadIdx.x; q < kMatF * S.nmat; q += B) lm[q] = S.mat[q];
+        if (BRUTE == 3) {   // the clustered loop's item tests read their slots here
+            float4* lc = reinterpret_cast<float4*>(lm + kMatF * S.nmat);
+            for (int q = threadIdx.x; q < 2 * S.ncslot; q += B) lc[q] = S.brute_cbox[q];
+            boxrec = lc;
+        }
         __syncthreads();
         mtrec = lr;
         tshade = ls;
@@ -293,7 +298,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         const rtm_f3 to = (phase == PRIMARY) ? C.position : Bo;
         const rtm_f3 td = (phase == PRIMARY) ? cd : ((phase == BOUNCE) ? Bd : C.sun);
         const unsigned long long t_tr = COUNT ? clock64() : 0;
-        const Hit h = trace<TRAV, COUNT, SMEM, OVF, BRUTE != 0>(S, nodes, tris, to, td, stk, B, lst, c, mtrec, ts, boxrec);
+        const Hit h = trace<TRAV, COUNT, SMEM, OVF, BRUTE != 0, BRUTE == 3>(S, nodes, tris, to, td, stk, B, lst, c, mtrec, ts, boxrec);
         if (COUNT && lane == __ffsll((long long)__ballot(1)) - 1) {   // the first tracing lane, once per wave
             const unsigned long long dt = clock64() - t_tr;
             c.cyc_trav += dt;
@@ -944,17 +949,32 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     if (TRAV == TRAV_FAST && sc.nbrute > 0) lds = std::max(lds, (size_t)(block / 64) * BRUTE_WAVE_LDS);
     if (BRUTE)
         lds = (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.nbox * 32 +
-              (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF);
+              (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32;
     if (SMEM) lds += (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
     if (fp.nloc <= 0) return hipSuccess;
     // persistent grid: as many blocks as the device keeps resident (pixels are handed out by d_work)
     int dev = 0, cus = 0, per_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    // clustered scenes (DevScene::ncluster > 0) run the one-lane product kernel with the clustered loop (BRUTE = 3);
+    // the instrumented build and every other scene keep the lock-step loop over brute_box (BRUTE = 1)
+    constexpr int kBruteClu = (BRUTE && !COUNT && !LOG) ? 3 : BRUTE ? 1 : 0;
+    bool clu = kBruteClu == 3 && sc.ncluster > 0;
     const void* kfn = RESUME ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>
                              : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>;
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, block, lds);
     if (e != hipSuccess) return e;
+    // auto: only tiles with at least one pixel per resident lane.  Measured on C2: the whole
+    // frame (3.2 pixels per lane) 7.29 -> 7.02 ms, the 1/8 tile (0.4 per lane: half-empty waves that wait on
+    // the LDS round trips of the item batches instead of on VALU issue) 2.14 -> 2.23 ms
+    if (clu && sc.cluster_auto &&
+        fp.nloc < (int64_t)std::max(1, cus) * std::max(1, per_cu) * block)
+        clu = false;
+    if (clu) {
+        kfn = (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu, ACC>;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, block, lds);
+        if (e != hipSuccess) return e;
+    }
     // blocks per CU for at most max_waves waves per SIMD (4 SIMDs per CU)
     const int cap_cu = fp.max_waves > 0 ? std::max(1, fp.max_waves * 4 * 64 / block) : INT_MAX;
     const int64_t resident = (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu, cap_cu));
@@ -1035,6 +1055,9 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
                            sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else if (BRUTE && f.team > 1)
         hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>), dim3((unsigned)grid),
+                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
+    else if (clu)
+        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu, ACC>), dim3((unsigned)grid),
                            dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else
         hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>), dim3((unsigned)grid),
@@ -1197,7 +1220,8 @@ hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, flo
     }
     // BRUTE stages the scene in LDS: only while two blocks still fit a CU
     const size_t brute_lds = (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 +
-                             (size_t)sc.nbox * 32 + (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF);
+                             (size_t)sc.nbox * 32 + (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) +
+                             (size_t)sc.ncslot * 32;
     if (sc.ntri > 0 && sc.nbrute > 0 && brute_lds <= 80 * 1024)
         return launch_t<TRAV_FAST, COUNT, false, false, false, false, true, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work,
                                                                             stream);
@@ -1354,7 +1378,8 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
     // a set number of trails, or (spec < 0) chosen on the device with the team size
     const bool spec_ok = traversal == TRAV_FAST && fp.spec != 0 && fp.spec_log && fp.pilot_draws && spec_walk(sc, fp);
     if (spec_ok && fp.spec > 0) return launch_spec(sc, b, block, d_out, d_work, stream);
-    if (fp.walk_team == 0 && traversal == TRAV_FAST) {
+    // (the brute-force kernels take their team size from the tile, launch_t: no pick, no read-back)
+    if (fp.walk_team == 0 && traversal == TRAV_FAST && sc.nbrute == 0) {
         // pass 2's team size from the pixels pass 1 left unfinished (pilot_team_pick_kernel)
         static_assert(kTeamOffset >= kGroups * kCounterStride && kTeamOffset + 8 <= kConstOffset, "work block layout");
         unsigned* left = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_work) + kTeamOffset);

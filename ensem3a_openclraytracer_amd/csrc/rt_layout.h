@@ -22,6 +22,22 @@ constexpr int kMaxLanesPerCu = 2048;   // resident threads per CU (gfx950)
 #define RT_BOX_GROUP 4
 #endif
 constexpr int kBoxGroup = RT_BOX_GROUP;  // leaf boxes per scalar load group of the brute-force loop (DevScene::brute_box)
+// Clustered brute force (DevScene::brute_cbox, option "brute_cluster"): a cluster holds up to kClusterSlots
+// distinct leaf boxes in kClusterSlots slots (padded), so an item index splits into (owner, box) with a
+// shift and a mask.  A subtree of m boxes whose union has the share p of the root's surface area becomes a
+// cluster when its estimated cost 1 + kappa p kClusterSlots (one union test, then the passing rays'
+// compacted (ray, box) items, padding slots included) is below kClusterGain m (m lock-step tests; 3/4: "clearly
+// below").  kappa = the VALU instructions -- the kernel is bound by VALU issue, DESIGN.md 5.1 -- a wave issues
+// per batch of 64 compacted items over those per lock-step box, counted in the built gfx950 kernel (DESIGN.md
+// 5.2): 62 (owner-list and LDS table addressing, slab test, two ring writes) against 32 (22 slab + 10 queue).
+constexpr int kClusterShift = 3;
+constexpr int kClusterSlots = 1 << kClusterShift;
+constexpr double kClusterKappa = 1.9;
+constexpr double kClusterGain = 0.75;
+// a cluster whose union more than kClusterLockNum / 8 of the wave's tracing lanes pass runs its slots
+// lock-step: n passing lanes cost n kClusterSlots / nact item batches against kClusterSlots lock-step
+// boxes, equal at n = nact / kappa = 0.53 nact
+constexpr int kClusterLockNum = 4;
 #ifndef RT_BRUTE_MAX_DEFAULT
 #define RT_BRUTE_MAX_DEFAULT 64   // FAST tests every triangle of scenes up to this size (rt_set_option "brute_max")
 #endif

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -385,12 +386,128 @@ void emit_bvh(HostScene& hs, const int32_t* L, const int32_t* R, const int32_t* 
     emit_wide(hs, L, R, T, box, nn);
 }
 
+// The clustered form of the brute-force boxes (HostScene::brute_cbox / brute_crow; option "brute_cluster",
+// mode 0 off, < 0 auto, > 0 force): the SAH regrouping of the distinct leaf boxes is cut, top-down, into
+// subtrees of 2..kClusterSlots boxes that become clusters -- mode auto: where the estimated cost of one
+// union test plus the passing rays' compacted items is clearly below the subtree's lock-step tests
+// (rt_layout.h kClusterKappa, kClusterGain; p = the union's surface area over the root's, the chance that
+// a ray through the scene crosses it); mode force: every such subtree -- and single slots.
+// brute_cbox: the single slots in brute_box order, padded with pad_box() to whole groups of kBoxGroup, then
+// kClusterSlots slots per cluster (its boxes in brute_box order, padded likewise).  A cluster's row holds the
+// componentwise minimum / maximum of its members' bounds (one ulp further out where a flat member lies on
+// it, below): slab() is monotone in the bounds, so a ray that passes a member passes the union.  Clusters
+// hold finite boxes only.  brute_box itself is untouched.
+void build_clusters(HostScene& hs, int mode) {
+    hs.brute_cbox.clear();
+    hs.brute_crow.clear();
+    hs.ncluster = 0;
+    hs.nsingle = 0;
+    const int32_t n = hs.nbox;
+    if (mode == 0 || n < 2) return;
+    std::vector<float> lb(6 * (size_t)n);
+    std::vector<int32_t> ids((size_t)n);
+    for (int32_t g = 0; g < n; ++g) {
+        const float* b = hs.brute_box.data() + 8 * (size_t)g;
+        float* o = lb.data() + 6 * (size_t)g;
+        o[0] = b[0]; o[1] = b[2]; o[2] = b[4]; o[3] = b[1]; o[4] = b[3]; o[5] = b[5];
+        ids[g] = g;
+    }
+    rt::SahTree st;
+    rt::sah_build(lb.data(), ids.data(), n, st);
+    std::vector<int32_t> cnt(st.L.size(), 0);
+    std::function<int32_t(int32_t)> count = [&](int32_t i) {
+        return cnt[i] = st.L[i] < 0 ? 1 : count(st.L[i]) + count(st.R[i]);
+    };
+    count(0);
+    auto area = [&](int32_t i) {
+        const float* b = st.box.data() + 6 * (size_t)i;
+        const double x = (double)b[3] - b[0], y = (double)b[4] - b[1], z = (double)b[5] - b[2];
+        return x * y + y * z + z * x;
+    };
+    std::function<void(int32_t, std::vector<int32_t>&)> collect = [&](int32_t i, std::vector<int32_t>& out) {
+        if (st.L[i] < 0) {
+            out.push_back(st.leaf[i]);
+            return;
+        }
+        collect(st.L[i], out);
+        collect(st.R[i], out);
+    };
+    const double root = area(0);
+    std::vector<int32_t> singles;
+    std::vector<std::vector<int32_t>> clusters;
+    std::function<void(int32_t)> cut = [&](int32_t i) {
+        if (st.L[i] < 0) {
+            singles.push_back(st.leaf[i]);
+            return;
+        }
+        const int32_t m = cnt[i];
+        if (m <= rt::kClusterSlots) {
+            std::vector<int32_t> mem;
+            collect(i, mem);
+            bool take = true;
+            for (int32_t g : mem)
+                for (int k = 0; k < 6; ++k) take = take && std::isfinite(hs.brute_box[8 * (size_t)g + k]);
+            if (take && mode < 0) {
+                const double p = root > 0.0 && std::isfinite(root) ? std::min(1.0, area(i) / root) : 1.0;
+                take = 1.0 + rt::kClusterKappa * p * rt::kClusterSlots < rt::kClusterGain * m;
+            }
+            if (take) {
+                std::sort(mem.begin(), mem.end());
+                clusters.push_back(mem);
+                return;
+            }
+        }
+        cut(st.L[i]);
+        cut(st.R[i]);
+    };
+    cut(0);
+    if (clusters.empty()) return;
+    std::sort(singles.begin(), singles.end());
+    std::sort(clusters.begin(), clusters.end());
+    const size_t ns4 = (singles.size() + rt::kBoxGroup - 1) / rt::kBoxGroup * rt::kBoxGroup;
+    const size_t nslot = ns4 + clusters.size() * rt::kClusterSlots;
+    hs.brute_cbox.assign(8 * nslot, 0.0f);
+    for (size_t s = 0; s < nslot; ++s) pad_box(hs.brute_cbox.data() + 8 * s);
+    auto put = [&](size_t s, int32_t g) {
+        std::memcpy(hs.brute_cbox.data() + 8 * s, hs.brute_box.data() + 8 * (size_t)g, 8 * sizeof(float));
+    };
+    for (size_t s = 0; s < singles.size(); ++s) put(s, singles[s]);
+    hs.brute_crow.assign(8 * clusters.size(), 0.0f);
+    for (size_t c = 0; c < clusters.size(); ++c) {
+        const size_t first = ns4 + c * rt::kClusterSlots;
+        float* r = hs.brute_crow.data() + 8 * c;
+        for (size_t j = 0; j < clusters[c].size(); ++j) {
+            put(first + j, clusters[c][j]);
+            const float* b = hs.brute_box.data() + 8 * (size_t)clusters[c][j];
+            for (int k = 0; k < 6; ++k)
+                r[k] = j == 0 ? b[k] : (k & 1) ? std::max(r[k], b[k]) : std::min(r[k], b[k]);
+        }
+        // a member that is flat on an axis (lo = hi = v: an axis-aligned face) passes a ray that lies in its
+        // plane with a zero direction component there: both its slab distances are 0 * inf = NaN and the axis
+        // drops out.  A union bound equal to v would give that ray one NaN and one infinite distance, and
+        // reject it; one ulp further out both distances are infinite, of opposite signs, and the axis drops
+        // out of the union test as well
+        for (int32_t g : clusters[c]) {
+            const float* b = hs.brute_box.data() + 8 * (size_t)g;
+            for (int a = 0; a < 3; ++a) {
+                if (b[2 * a] != b[2 * a + 1]) continue;
+                if (r[2 * a] == b[2 * a]) r[2 * a] = std::nextafterf(r[2 * a], -INFINITY);
+                if (r[2 * a + 1] == b[2 * a]) r[2 * a + 1] = std::nextafterf(r[2 * a + 1], INFINITY);
+            }
+        }
+        r[6] = as_f32((int32_t)first);
+        r[7] = as_f32((int32_t)clusters[c].size());
+    }
+    hs.ncluster = (int32_t)clusters.size();
+    hs.nsingle = (int32_t)singles.size();
+}
+
 // Pack the FAST layout from the reference export.  Returns false (with
 // reason) if the export is not a proper binary tree with one triangle per
 // leaf, in which case only the REF traversal is available.  layout
 // RT_BVH_REFERENCE keeps the reference's tree, RT_BVH_SAH regroups its leaf
 // boxes (bvh_sah.cpp); both give the same hits.
-bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int layout, int brute_max,
+bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int layout, int brute_max, int cluster,
                std::string& why) {
     if (nn <= 0) {
         why = "empty BVH";
@@ -466,6 +583,10 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
     hs.brute_box.clear();
     hs.nbrute = 0;
     hs.nbox = 0;
+    hs.brute_cbox.clear();
+    hs.brute_crow.clear();
+    hs.ncluster = 0;
+    hs.nsingle = 0;
     if ((int64_t)leaves.size() <= (int64_t)brute_max) {
         std::vector<int32_t> by_rank(leaves.size());
         for (int32_t n : leaves) by_rank[rank[T[n]]] = n;
@@ -518,6 +639,7 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
                 pad_box(b);
             }
         }
+        build_clusters(hs, cluster);
     }
     if (layout == RT_BVH_SAH && leaves.size() > 1) {
         std::vector<float> lb(6 * leaves.size());
@@ -543,9 +665,9 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
 
 namespace rt {
 
-void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max,
+void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
                   std::string& why) {
-    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, why) : true;
+    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, why) : true;
     if (hs.fast_ok && ntri > 0) {
         // the FAST kernels' Moller-Trumbore reciprocal (rt_device.h mt_recip) is IEEE-exact for
         // |a| <= 2^126, a = e1 . (d x e2) with |d| = 1: bound |e1| |e2| (finite edges; an infinite or
@@ -569,6 +691,7 @@ void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, in
         hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0;
     }
     if (!hs.fast_ok) { hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0; }
+    if (hs.nbrute == 0) { hs.brute_cbox.clear(); hs.brute_crow.clear(); hs.ncluster = 0; hs.nsingle = 0; }
     if (!hs.fast_ok || hs.wdepth > 64) { hs.wnodes.clear(); hs.wleaves.clear(); hs.nwnodes = 0; hs.wdepth = 1; }
     // render kernels keep kStackLds entries in LDS and spill deeper ones to HBM; the single-ray
     // debug kernel keeps the whole stack in LDS (int2 entries, 128 lanes): depth <= 64
@@ -588,7 +711,7 @@ namespace {
 
 int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                    int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                   int brute_max, std::string& msg, std::string& why) {
+                   int brute_max, int cluster, std::string& msg, std::string& why) {
     if (nvp < 0 || nvp % 3 || nvn < 0 || nvn % 3 || nface < 0 || nface % 10 || nmat <= 0 || nmat % 6 || nbvh < 0 ||
         nbvh % 9)
         return fail(msg, RT_ERR_ARG,
@@ -665,7 +788,7 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
             }
         }
     }
-    pack_checked(hs, bvh9, NB, T, layout, brute_max, why);
+    pack_checked(hs, bvh9, NB, T, layout, brute_max, cluster, why);
     return RT_OK;
 }
 
@@ -674,9 +797,10 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
 // No C++ exception leaves the C ABI: a scene too large for host memory is an error status.
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, std::string& msg, std::string& why) {
+                  int brute_max, int cluster, std::string& msg, std::string& why) {
     try {
-        return scene_prepare_(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout, brute_max, msg, why);
+        return scene_prepare_(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout, brute_max, cluster, msg,
+                              why);
     } catch (const std::bad_alloc&) {
         hs = HostScene();
         return fail(msg, RT_ERR_ARG, "scene too large for host memory");
@@ -702,7 +826,7 @@ extern "C" int rt_scene_check(const float* vp, int64_t nvp, const float* vn, int
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc == RT_OK && info) {
         info[0] = hs.ntri;
@@ -733,7 +857,7 @@ extern "C" int rt_debug_brute_layout(const float* vp, int64_t nvp, const float* 
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.nbox;
@@ -741,5 +865,37 @@ extern "C" int rt_debug_brute_layout(const float* vp, int64_t nvp, const float* 
     info[2] = (int64_t)hs.brute_box.size();
     const int64_t n = std::min<int64_t>(cap, info[2]);
     if (n > 0) std::memcpy(boxes, hs.brute_box.data(), (size_t)n * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_brute_clusters(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                       int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                       int layout, int cluster, float* slots, int64_t slot_cap, float* rows,
+                                       int64_t row_cap, int64_t info[4]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (cluster < -1 || cluster > 1) {
+        g_check_error = "brute_cluster must be -1 (auto), 0 (off) or 1 (force)";
+        return RT_ERR_ARG;
+    }
+    if (!info || slot_cap < 0 || row_cap < 0 || (slot_cap > 0 && !slots) || (row_cap > 0 && !rows)) {
+        g_check_error = "null info, or a capacity without an array";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, cluster, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[0] = hs.ncluster;
+    info[1] = hs.nsingle;
+    info[2] = (int64_t)hs.brute_cbox.size();
+    info[3] = (int64_t)hs.brute_crow.size();
+    const int64_t ns = std::min<int64_t>(slot_cap, info[2]), nr = std::min<int64_t>(row_cap, info[3]);
+    if (ns > 0) std::memcpy(slots, hs.brute_cbox.data(), (size_t)ns * sizeof(float));
+    if (nr > 0) std::memcpy(rows, hs.brute_crow.data(), (size_t)nr * sizeof(float));
     return RT_OK;
 }

@@ -27,6 +27,10 @@ struct HostScene {
     std::vector<float> brute_box;  // 8 floats per triangle, padded to whole groups (DevScene::brute_box)
     int32_t nbrute = 0;
     int32_t nbox = 0;              // distinct leaf boxes in brute_box (records with bit-identical boxes share one)
+    // the clustered form of brute_box (DevScene::brute_cbox / brute_crow; ncluster = 0: not clustered)
+    std::vector<float> brute_cbox; // 8 floats per slot: the single slots padded to whole groups, then kClusterSlots per cluster
+    std::vector<float> brute_crow; // 8 floats per cluster: union lo.x hi.x lo.y hi.y lo.z hi.z | first slot, box count
+    int32_t ncluster = 0, nsingle = 0;   // clusters; single (real) slots at the head of brute_cbox
     int32_t nnodes = 0, root_ref = 0, ntri = 0, nmat = 0, nbvh9 = 0, depth = 1;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     bool fast_ok = false;
@@ -40,10 +44,11 @@ struct HostScene {
 // reason when the FAST layouts are unavailable (hs.fast_ok false; the REF traversal then serves).
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, std::string& msg, std::string& why);
+                  int brute_max, int cluster, std::string& msg, std::string& why);
 
 // pack_fast + the limits of the FAST kernels; sets hs.fast_ok (an option change repacks with it).
-void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max,
+// cluster: option "brute_cluster" (0 off, -1 auto, 1 force; include/rt_debug.h).
+void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
                   std::string& why);
 
 }  // namespace rt

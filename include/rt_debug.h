@@ -13,6 +13,8 @@
  *   "resume_min"   resumable tree walk: shade once this many of 64 lanes are free (-1 auto 36 / 48)
  *   "step"         tree-walk traversal loop: 1 one item per step, 2 descend-until-leaf rounds (0 auto)
  *   "team"         brute force: lanes per pixel 1/2/4/8 (0 auto by tile size)
+ *   "brute_cluster"  brute force, one lane per pixel: groups of leaf boxes behind one union test, the passing
+ *                  rays' (ray, box) tests compacted (0 off, 1 every SAH subtree of 2..8 boxes, -1 auto by cost)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
  *   "spec"         pass 2 of a pilot launch: speculative trails per pixel 2/4/8 (0 off, -1 auto)
  *   "slices"       one-pass tree-walk launches: sample slices per pixel 2..16 (0 off, -1 auto)
@@ -90,6 +92,18 @@ int rt_debug_quantise_axis(float p, const float* lo, const float* hi, int n, flo
 int rt_debug_brute_layout(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
                           int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
                           int layout, float* boxes, int64_t cap, int64_t info[3]);
+
+/* Host-only (no device): the clustered form of that array which option "brute_cluster" = cluster (-1 auto,
+ * 0 off, 1 force) makes rt_set_scene upload beside it.  info[0] = clusters (0: not clustered, both arrays
+ * empty), info[1] = single real slots, info[2] = floats in the slot array: 8 per slot as above -- the single
+ * slots padded to a whole group of 4, then 8 slots per cluster, its real boxes first --, info[3] = floats in
+ * the row array, 8 per cluster: the union box lo.x hi.x lo.y hi.y lo.z hi.z, then the int bits of the
+ * cluster's first slot and of its box count.  Every real slot of rt_debug_brute_layout's array appears
+ * once; every padding slot lists record 0 alone. */
+int rt_debug_brute_clusters(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                            int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                            int layout, int cluster, float* slots, int64_t slot_cap, float* rows, int64_t row_cap,
+                            int64_t info[4]);
 
 #ifdef __cplusplus
 }
