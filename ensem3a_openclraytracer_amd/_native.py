@@ -34,7 +34,7 @@ EXPORTED = (
     "rt_accum_begin_device", "rt_accum_add_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
-    "rt_debug_brute_clusters",
+    "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
@@ -129,6 +129,8 @@ def lib():
                                              _c_p]),
             "rt_debug_brute_clusters": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32,
                                                _c_p, _i64, _c_p, _i64, _c_p]),
+            "rt_debug_brute_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _c_p]),
+            "rt_debug_last_slices": (_i32, []),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
@@ -486,6 +488,21 @@ def brute_clusters(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, lay
     if st != 0:
         raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
     return slots.reshape(-1, 8), rows.reshape(-1, 8), int(info[1])
+
+
+def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: int = -1):
+    """rt_debug_brute_slices (include/rt_debug.h): ``(on, K, tail)`` of the sample-slice rule for brute-force
+    scenes, evaluated on the host alone."""
+    out = np.zeros(3, np.int32)
+    st = lib().rt_debug_brute_slices(int(nloc), int(lanes), int(spp), int(option), int(accum_base), out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_debug_brute_slices: bad arguments")
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
+def last_slices() -> int:
+    """rt_debug_last_slices: the slice word the last render launch's kernel got (0: unsliced)."""
+    return int(lib().rt_debug_last_slices())
 
 
 def tile_rows(npix: int, width: int, row0: int, row_step: int) -> int:

@@ -603,7 +603,7 @@ namespace {
 constexpr int kSlicesWide = 8;
 constexpr int kSlicesWideSmall = 12;
 constexpr int64_t kSlicesMinPerLane = 4;
-constexpr int kAccumSliceMin = 8;
+using rt::kAccumSliceMin;   // (rt_slices.h, with the brute-force scenes' rule)
 
 // Two-pass launches (FrameParams::pass): FAST tree-walk renders of tiles with more pixels than the
 // device keeps lanes resident get a pilot pass of spp / 8 samples (option "pilot": -1 auto, 0 off,
@@ -688,19 +688,25 @@ namespace {
 // N=4 1,395 / 1,273 / 1,221 / 1,197, N=2 2,536 / 2,409 / 2,361 / 2,343, N=1 4,796 / 4,692 / 4,642 / 4,648
 // (the wave cap of 6 instead: 838 / 1,444 / 2,651 / 5,066).  Sets fp's slice fields, sizes the device's
 // state buffer and zeroes the samples-done words on stream s (the launch's stream).
+// Brute-force scenes (r09): the one-lane kernels take slices too, K = kSlicesBrute on auto, decided at the launch.
 hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t s, int accum_base = -1) {
     fp.slices = 0;
-    if (effective_traversal(ctx) != RT_TRAVERSAL_FAST || fp.nloc <= 0 || ctx->hs.nbrute > 0 || fp.resume_min <= 0 ||
-        ctx->slices == 0)
+    // brute-force scenes (the one-lane kernels, render_kernel): one-pass launches; K on auto is handed on as
+    // -K, and the launch decides where it knows its kernel's resident lanes (rt_kernels.hip launch_t), which
+    // also zeroes the samples-done words when it takes slices
+    const bool brute = ctx->hs.nbrute > 0;
+    if (effective_traversal(ctx) != RT_TRAVERSAL_FAST || fp.nloc <= 0 || ctx->slices == 0 ||
+        (brute ? fp.pilot > 0 : fp.resume_min <= 0))
         return hipSuccess;
     const int64_t lanes = (int64_t)std::max(d.cus, 1) * rt::kWalkLanesPerCu;
     // pilot launches: pass 2 slices the samples after the pilot's when the device gives it one lane per pixel
     // (pilot_team_pick_kernel: more unfinished pixels than lanes); the team and trail kernels take none
     int k = ctx->slices > 0 ? ctx->slices
-                            : (use_wide(ctx) || fp.pilot > 0 || fp.nloc >= kSlicesMinPerLane * lanes) ? kSlicesWide : 1;
+            : brute        ? rt::kSlicesBrute
+                           : (use_wide(ctx) || fp.pilot > 0 || fp.nloc >= kSlicesMinPerLane * lanes) ? kSlicesWide : 1;
     // the 4-wide walk's small tiles (under kSlicesMinPerLane pixels per resident lane: C5's eighth, 2.26) take
     // finer slices: 1/8 tile 629.7 / 620.8 ms at 8 / 12 (whole frame 4,594 / 4,612: 8 kept there)
-    if (ctx->slices < 0 && use_wide(ctx) &&
+    if (ctx->slices < 0 && !brute && use_wide(ctx) &&
         fp.nloc < kSlicesMinPerLane * (int64_t)std::max(d.cus, 1) * rt::kWideWaves * 4 * 64)
         k = kSlicesWideSmall;
     // every slice at least two samples; accum_base >= 0: an add of a progressive accumulation, whose slices
@@ -709,18 +715,23 @@ hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t
     const int todo = fp.spp - std::max(fp.pilot, 0) - std::max(accum_base, 0);
     k = std::min(k, todo / 2);
     if (accum_base >= 0 && ctx->slices < 0) k = std::min(k, todo / kAccumSliceMin);
-    if (k <= 1 || (int64_t)fp.nloc * k >= ((int64_t)1 << 32)) return hipSuccess;
+    // brute-force scenes: the same bounds, from the rule the tests evaluate (rt_slices.h); K on auto goes on as -K
+    const int offer = brute ? rt::brute_slice_offer(ctx->slices, todo, accum_base >= 0) : 0;
+    if (brute) k = offer < 0 ? -offer : offer;
+    if (k <= 1 || (int64_t)fp.nloc * (k + (brute ? 1 : 0)) >= ((int64_t)1 << 32))
+        return hipSuccess;   // (the hand-out's job counters fit a word: take_pixel, take_job)
     const size_t n = (size_t)fp.nloc;
-    const size_t need = n * 32 + n * sizeof(uint32_t);
+    const size_t sbytes = brute ? 48 : 32;   // (the brute-force kernels' state carries the camera ray, slice_publish)
+    const size_t need = n * sbytes + n * sizeof(uint32_t);
     hipError_t e = hipSuccess;
     // growing frees the old buffer from the host: the last launch (any stream) may still use it
     if (d.slice.bytes < need && d.pending) e = hipEventSynchronize(d.done);
     if (e == hipSuccess) e = ensure(d.slice, need);
-    if (e == hipSuccess) e = hipMemsetAsync((char*)d.slice.p + n * 32, 0, n * sizeof(uint32_t), s);
+    if (e == hipSuccess && !brute) e = hipMemsetAsync((char*)d.slice.p + n * sbytes, 0, n * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    fp.slices = k;
+    fp.slices = brute ? offer : k;
     fp.slice_state = (float4*)d.slice.p;
-    fp.slice_ready = (uint32_t*)((char*)d.slice.p + n * 32);
+    fp.slice_ready = (uint32_t*)((char*)d.slice.p + n * sbytes);
     return hipSuccess;
 }
 
@@ -1128,6 +1139,9 @@ int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix
     HIP_OR_RET(ctx, ensure(d.counts, sizeof h));
     HIP_OR_RET(ctx, hipMemsetAsync(d.counts.p, 0, sizeof h, d.stream));
     HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    // the instrumented brute-force launch takes sample slices as the product launch does (the tree walk's
+    // counts are those of its unsliced frame)
+    if (ctx->hs.nbrute > 0) HIP_OR_RET(ctx, setup_slices(ctx, d, fp, d.stream));
     HIP_OR_RET(ctx, rt::launch_render(dev_scene(ctx, d), fp, effective_traversal(ctx), ctx->block, (float*)d.out.p,
                                       (unsigned long long*)d.counts.p, (unsigned int*)d.work.p, d.stream));
     HIP_OR_RET(ctx, mark_launch(d, d.stream));
@@ -1257,6 +1271,18 @@ int rt_debug_pixel_log(rt_ctx* ctx, int traversal, const float cam[10], const fl
     *n_events = n;
     return RT_OK;
 }
+
+int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int accum_base, int32_t out[3]) {
+    if (!out || nloc < 0 || lanes < 0 || option < -1 || option > 16) return RT_ERR_ARG;
+    const int todo = spp - std::max(accum_base, 0);
+    const int v = rt::brute_slice_launch(rt::brute_slice_offer(option, todo, accum_base >= 0), nloc, lanes);
+    out[0] = v != 0;
+    out[1] = v & 0xff;
+    out[2] = v >> 8;
+    return RT_OK;
+}
+
+int rt_debug_last_slices(void) { return rt::last_launch_slices(); }
 
 int rt_debug_timings(rt_ctx* ctx, double out[4]) {
     if (!ctx || !out) return set_err(ctx, RT_ERR_ARG, "bad arguments");

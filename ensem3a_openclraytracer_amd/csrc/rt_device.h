@@ -1028,6 +1028,121 @@ __device__ __forceinline__ unsigned take_pixel(PixelQueue& Q, unsigned long long
     return q;
 }
 
+// take_pixel for the sliced brute-force launches (render_kernel SLICED; a function of its own, so that take_pixel
+// and the kernels that call it stay what they were).  Only the last tail / 256 (1..256) of each group's pixels are
+// sliced: the group first hands out the pixels before them as whole jobs, then the slices of the rest,
+// slice-major.  Returns the pixel (nloc: none left) and in job_slice its slice, kWholeJob for a whole
+// pixel -- no job number for the caller to divide.
+constexpr unsigned kWholeJob = 0xffffffffu;
+__device__ __forceinline__ unsigned take_job(PixelQueue& Q, unsigned long long need, int lane0,
+                                             unsigned* __restrict__ counters, unsigned nloc, int lane,
+                                             unsigned slices, unsigned tail, unsigned& job_slice) {
+    const bool mine = (need >> lane0) & 1ull;
+    const unsigned rank = (unsigned)__popcll(need & ((1ull << lane0) - 1ull));
+    const unsigned total = (unsigned)__popcll(need);
+    const int leader = __ffsll((long long)need) - 1;
+    unsigned q = nloc;
+    unsigned base = 0;   // requests served so far
+    unsigned g = blockIdx.x % (unsigned)kGroups;
+    for (int t = 0; t < kGroups && base < total; ++t, g = (g + 1u) % (unsigned)kGroups) {
+        if ((Q.dry >> g) & 1u) continue;
+        const unsigned k = total - base;
+        unsigned got = 0;
+        if (lane == leader) got = atomicAdd(counters + g * (unsigned)(kCounterStride / 4), k);
+        const unsigned j0 = (unsigned)__builtin_amdgcn_readfirstlane((int)__shfl(got, leader, 64));
+        const unsigned px = group_pixels(g, nloc, Q.per);
+        const unsigned pw = px - (unsigned)(((unsigned long long)px * tail) >> 8);   // whole jobs
+        const unsigned ps = px - pw;                                                  // sliced pixels
+        const unsigned have = pw + ps * slices;
+        const unsigned nok = j0 < have ? min(have - j0, k) : 0u;
+        if (mine && rank >= base && rank < base + nok) {
+            const unsigned jj = j0 + (rank - base);
+            if (jj < pw) {
+                q = group_pixel(g, jj, Q.per);
+                job_slice = kWholeJob;
+            } else {   // (jj >= pw and jj < have: ps > 0)
+                const unsigned jr = jj - pw, ks = jr / ps;
+                q = group_pixel(g, pw + (jr - ks * ps), Q.per);
+                job_slice = ks;
+            }
+        }
+        if (nok < k) Q.dry |= 1u << g;   // the group's sequence has run past the tile
+        base += nok;
+    }
+    return q;
+}
+
+// ---- sample slices (FrameParams::slices): a pixel's state handed from the job of one slice to the next ----
+// (shared by the tree walk, render_resume_kernel, and the one-lane brute-force kernels, render_kernel)
+
+// the sample count slice k of a pixel ends at: nsl slices over the samples sb .. spp - 1
+__device__ __forceinline__ int slice_end(int sb, int spp, unsigned nsl, unsigned k) {
+    return sb + (int)((k + 1u) * (unsigned)(spp - sb) / nsl);
+}
+
+// The pixel's state after a job's slice, stored write-through (sc1) for the lane that runs the next slice (st: the
+// pixel's record); then, once the wave's stores have completed, the samples done (the word that lane polls).
+// w: the cached camera hit's triangle (the brute-force kernels pack the cached shadow-ray hit beside it).
+// cd (the brute-force kernels, whose records are 48 bytes: render_kernel): the camera ray's direction behind the
+// tree walk's 32 bytes, so that a job that continues a pixel computes nothing from the pixel's number
+__device__ __forceinline__ unsigned long long slice_pack(float a, float b) {
+    return (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32);
+}
+__device__ __forceinline__ void slice_publish(const FrameParams& F, gu64* st, int p, rtm_f3 acc, float kc,
+                                              uint32_t seed0, uint32_t seed1, unsigned w, int s,
+                                              bool with_cd = false, rtm_f3 cd = rtm_v3(0, 0, 0)) {
+    __hip_atomic_store(st + 0, slice_pack(acc.x, acc.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st + 1, slice_pack(acc.z, kc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st + 2, (unsigned long long)seed0 | ((unsigned long long)seed1 << 32), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st + 3, (unsigned long long)w | ((unsigned long long)(unsigned)s << 32),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (with_cd) {
+        __hip_atomic_store(st + 4, slice_pack(cd.x, cd.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(st + 5, slice_pack(cd.z, 0.0f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // The hand-off is built by hand, not as a release / acquire pair: at agent scope those compile on
+    // gfx950 to an L2 write-back (buffer_wbl2 sc1) before every ready store and an L2 invalidate
+    // (buffer_inv sc1) after every successful poll -- of the whole L2 the BVH lives in -- measured
+    // C3 106.9 -> 152.8 ms, C4 272.8 -> 297.1, C5 4,485 -> 5,705 ms (r06).  Here the
+    // state words and the count are sc1 (agent-scope) atomics, which write through to memory and
+    // read past this CU's L1; s_waitcnt vmcnt(0) orders the state stores' completion before the
+    // count store, and the reader's wavefront fence keeps its state loads after the poll.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store((gu32*)(F.slice_ready + p), (unsigned)s, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the poll of a job that waits for its pixel's previous slice: are need_s samples done?
+__device__ __forceinline__ bool slice_ready(const FrameParams& F, int p, unsigned need_s) {
+    const unsigned done_s = __hip_atomic_load((gu32*)(F.slice_ready + p), __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+    return done_s >= need_s;
+}
+
+// after a successful poll: the state the previous slice's lane published, read with sc1 loads (past this CU's L1)
+__device__ __forceinline__ void slice_take(gu64* st, rtm_f3& acc, float& kc, uint32_t& seed0, uint32_t& seed1,
+                                           unsigned& w, int& s) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // the state loads stay after the poll
+    const unsigned long long a = __hip_atomic_load(st + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long b = __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long d = __hip_atomic_load(st + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long e = __hip_atomic_load(st + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    acc = rtm_v3(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b));
+    kc = __uint_as_float((unsigned)(b >> 32));
+    seed0 = (uint32_t)d;
+    seed1 = (uint32_t)(d >> 32);
+    w = (unsigned)e;
+    s = (int)(unsigned)(e >> 32);
+}
+
+// ... and the camera ray's direction behind it (the brute-force kernels' records; issued with slice_take's loads)
+__device__ __forceinline__ rtm_f3 slice_take_cd(gu64* st) {
+    const unsigned long long f = __hip_atomic_load(st + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long g = __hip_atomic_load(st + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return rtm_v3(__uint_as_float((unsigned)f), __uint_as_float((unsigned)(f >> 32)), __uint_as_float((unsigned)g));
+}
+
 // ---- resumable FAST traversal (option "resume_min") ----
 // On deep scenes a wave's traversal loop runs until its slowest ray is done
 // (SIMD efficiency 13 % on C3/C4).  Here each lane keeps its traversal state in

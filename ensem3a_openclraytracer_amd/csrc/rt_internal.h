@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "rt_layout.h"
+#include "rt_slices.h"
 
 namespace rt {
 
@@ -136,6 +137,12 @@ struct FrameParams {
     // stores the pixel's state (slice_state: acc.xyz | kc, seed0 seed1 tc s; write-through) and then the
     // samples done (slice_ready); the job of the next slice, on any lane, waits for that count and
     // continues from the state.  Every pixel's samples run in order: the frame is the one-pass frame.
+    // Brute-force scenes (the one-lane kernels, one-pass launches; the three forms of this word are made in one
+    // place, rt_slices.h brute_slice_offer / brute_slice_launch): rt_api.hip hands K on, or -K for K on auto;
+    // launch_t decides from its kernel's resident lanes and gives the kernel K | tail << 8 -- only the last
+    // tail / 256 of the tile's pixels are sliced, the others are whole jobs handed out first (take_job) -- and
+    // the state is 48 bytes per pixel (+ the camera ray's direction; tc shares its word with the cached
+    // shadow-ray hit).
     int32_t slices;
     float4* slice_state;
     uint32_t* slice_ready;
@@ -201,6 +208,9 @@ hipError_t launch_spec(const DevScene& sc, const FrameParams& fp, int block, flo
                        hipStream_t stream);
 bool spec_walk(const DevScene& sc, const FrameParams& fp);
 // test hooks
+// FrameParams::slices as the kernel of the last launch_t got it (0: an unsliced launch)
+void note_launch_slices(int v);
+int last_launch_slices();
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream);
 hipError_t launch_debug_log(const DevScene& sc, const FrameParams& fp, int traversal, float* d_out,
                             unsigned int* d_work, hipStream_t stream);

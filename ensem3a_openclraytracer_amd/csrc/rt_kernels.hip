@@ -24,6 +24,8 @@
 //
 // Numerics: every OpenCL builtin of the reference is taken from rtm.h and the
 // file is compiled with -ffp-contract=off (see rtm.h).
+#include <atomic>
+
 #include "rt_device.h"
 
 namespace rt {
@@ -48,7 +50,11 @@ __device__ __forceinline__ void save_state(float4* __restrict__ st, int p, rtm_f
 // ACC: an add of a progressive accumulation (rt_internal.h: F.pilot_state its state, F.pilot the samples done,
 // one pass) -- instantiations of their own, so that
 // the one-shot kernels keep their code and registers
-template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE = 0, bool ACC = false>
+// BRUTE_: the brute-force loop (0 none, 1 lock-step, 2 teams, 3 clustered), + kBruteSliced for the launches
+// that hand out sample slices (FrameParams::slices; one lane per pixel: 1 and 3 only) -- instantiations of
+// their own again, so that an unsliced launch runs the code it ran without them
+constexpr int kBruteSliced = 4;
+template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, bool ACC = false>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
 // spills, the instrumented (COUNT) ones spill a few registers to scratch.
@@ -59,6 +65,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                                                unsigned long long* __restrict__ counts,
                                                unsigned int* __restrict__ work_counter,
                                                const LaunchConst* __restrict__ lconst) {
+    constexpr int BRUTE = BRUTE_ & 3;
+    constexpr bool SLICED = (BRUTE_ & kBruteSliced) != 0;
+    static_assert(!SLICED || BRUTE == 1 || BRUTE == 3, "sample slices: the one-lane brute-force loops");
     extern __shared__ int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
@@ -143,7 +152,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     int cost = 0;   // pass 1: rays this pixel traced (pilot_cost)
     int sun0 = -2;  // the first bounce's shadow-ray hit (-1 = miss; -2 = not traced yet)
     unsigned long long t_prev = 0;   // COUNT: the wave clock at the previous loop head
-
     // pass 1 (FrameParams::pass): after the pilot samples, save the pixel's state for pass 2; the
     // pixel is written (and its cost set to 0) when all its samples are done
     auto save_pilot = [&]() __attribute__((always_inline)) {
@@ -151,6 +159,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         F.pilot_state[2 * (int64_t)p + 1] =
             make_float4(__uint_as_float(seed0), __uint_as_float(seed1), __int_as_float(tc), __int_as_float(s));
         F.pilot_cost[p] = s >= spp ? 0u : (unsigned)cost;
+    };
+
+    // sample slices (SLICED; one-pass launches): as in render_resume_kernel, lim is the sample count this
+    // job stops at and, while the job waits for the slice before it (WAIT_SLICE), the job's slice index (s is
+    // then the sample count that slice ends at: the poll's operand).
+    // F.slices = K | tail << 8: only the last tail / 256 of the pixels are sliced, the rest are whole jobs handed
+    // out before them (take_pixel), so the hand-offs are paid where the frame ends and nowhere else.
+    // The hand-off carries sun0 beside tc (16 bits each: the scene is staged in LDS, ntri + 2 < 2^16,
+    // launch_t), so a pixel traces its first bounce's shadow ray once, not once per slice, and the camera
+    // ray's direction: a job that continues a pixel divides nothing and runs no camera_dir (with a job
+    // ending in nearly every round of a wave, that start-up is run by the whole wave every round)
+    const unsigned nsl = SLICED ? (unsigned)F.slices & 0xffu : 1u;
+    const unsigned stail = SLICED ? (unsigned)F.slices >> 8 : 0u;
+    const int sb = ACC ? F.pilot : 0;   // (ACC: the samples of earlier adds, rt_internal.h)
+    // slice_end (rt_device.h) without its division: (k + 1) n / K = (k + 1) (n / K) + (k + 1) (n % K) / K, the
+    // last quotient of a number below 16 x 15 by K <= 16 through a 16-bit reciprocal (exact below 2^16 / 15)
+    const unsigned sl_q = (unsigned)(spp - sb) / nsl, sl_r = (unsigned)(spp - sb) % nsl, sl_m = (65536u + nsl - 1u) / nsl;
+    auto send = [&](unsigned k) { return sb + (int)((k + 1u) * sl_q + (((k + 1u) * sl_r * sl_m) >> 16)); };
+    int lim = spp;
+    auto save_slice = [&](rtm_f3 cdv) __attribute__((always_inline)) {
+        slice_publish(F, (gu64*)(F.slice_state + 3 * (int64_t)p), p, acc, kc, seed0, seed1,
+                      (unsigned)(tc + 1) | ((unsigned)(sun0 + 2) << 16), s, true, cdv);
     };
 
     while (true) {
@@ -165,8 +195,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         // teams (BRUTE, F.team lanes per pixel): one bit per team, the team's lanes take the same pixel
         const unsigned long long need = __ballot(phase == FETCH) & team_leaders;
         if (need) {
-            const unsigned int q = take_pixel(pq, need, team_lane0, work_counter, nloc, lane);
-            if (phase == FETCH) {
+            unsigned sl = kWholeJob;   // SLICED: the job's slice, or a whole pixel
+            unsigned int q;
+            if constexpr (SLICED) q = take_job(pq, need, team_lane0, work_counter, nloc, lane, nsl, stail, sl);
+            else q = take_pixel(pq, need, team_lane0, work_counter, nloc, lane);
+            if (SLICED && phase == FETCH && q < nloc && sl != kWholeJob && sl > 0) {
+                // continues a pixel once its slice sl - 1 is done (below): all it needs is in that slice's state
+                p = (int)q;
+                lim = (int)sl;
+                s = send(sl - 1u);
+                phase = WAIT_SLICE;
+            } else if (phase == FETCH) {
+                const bool whole = !SLICED || sl == kWholeJob;
                 bool ok = q < nloc;
                 if (ok) {
                     p = F.pass == 2 ? (int)F.pilot_order[q] : (int)q;
@@ -177,8 +217,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                     i = (int)i64;
                 }
                 if (ok) {
-                    seed0 = (uint32_t)(i % imgSize);
-                    seed1 = (uint32_t)(i / imgSize);
+                    if constexpr (SLICED) {   // i < npix = imgSize (ok above; npix < 2^31, launch_t): no division
+                        seed0 = (uint32_t)i;
+                        seed1 = 0;
+                    } else {
+                        seed0 = (uint32_t)(i % imgSize);
+                        seed1 = (uint32_t)(i / imgSize);
+                    }
                     cd = camera_dir(C, W, i);
                     acc = rtm_v3(0, 0, 0);
                     s = 0;
@@ -210,16 +255,37 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                         so = rtm_v3(1, 1, 1);
                         phase = PREP;
                     }
+                    if constexpr (SLICED) lim = whole ? spp : send(0);
                 } else {
-                    // past the tile, or a padding pixel of a partial last row (its hand-out group, or pass 2's
-                    // cost order, may still hold real pixels): the lane retires once the queue is dry
+                    // past the tile, or a padding pixel of a partial last row (its hand-out group, pass 2's
+                    // cost order, or later sample slices may still hold real pixels): the lane retires once the queue is dry
+                    // (SLICED: slice 0 of a padding pixel says "all done" to the jobs of its later slices, which
+                    // do not look at the pixel's number)
+                    if constexpr (SLICED) { if (q < nloc && !whole) { s = spp; save_slice(cd); } }
                     phase = q < nloc ? FETCH : DONE;
                 }
             }
         }
+        if constexpr (SLICED) {
+            // the previous slice's samples done, published by the lane that ran it (save_slice): once the
+            // count is there the job continues from that lane's state, in this same iteration
+            if (phase == WAIT_SLICE && slice_ready(F, p, (unsigned)s)) {
+                unsigned w;
+                gu64* st = (gu64*)(F.slice_state + 3 * (int64_t)p);
+                slice_take(st, acc, kc, seed0, seed1, w, s);
+                cd = slice_take_cd(st);
+                tc = (int)(w & 0xffffu) - 1;
+                sun0 = (int)(w >> 16) - 2;
+                tri = tc; j = 0;
+                so = rtm_v3(1, 1, 1);
+                lim = send((unsigned)lim);
+                phase = s >= spp ? FETCH : PREP;   // finished early (a sample that draws nothing): written
+            }
+        }
         if (__all(phase == DONE)) break;
+        if (SLICED && __all(phase == DONE || phase == WAIT_SLICE)) __builtin_amdgcn_s_sleep(8);
         if (COUNT && lane == 0) c.wave_outer++;
-        if (phase == DONE || phase == FETCH) continue;   // FETCH: a pass-2 pixel finished in pass 1
+        if (phase == DONE || phase == FETCH || (SLICED && phase == WAIT_SLICE)) continue;   // FETCH: a pass-2 pixel finished in pass 1
 
         if (phase == PREP) {
             // naiveGI loop head for bounce j (Raytracing.cl:46-79); may complete samples without tracing
@@ -283,8 +349,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                     if (team_leader) store_pixel(out, p, acc, spp);
                     if (F.pass == 1) save_pilot();
                     if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
+                    if constexpr (SLICED) { if (lim < spp) save_slice(cd); }   // done early: its later slices find nothing to do
                 } else if (F.pass == 1 && s >= F.pilot) {
                     save_pilot();
+                    phase = FETCH;
+                } else if (SLICED && s >= lim) {
+                    save_slice(cd);
                     phase = FETCH;
                 } else {
                     tri = tc; j = 0;
@@ -375,9 +445,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 if (team_leader) store_pixel(out, p, acc, spp);
                 if (F.pass == 1) save_pilot();
                 if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
-                phase = FETCH;
+                phase = FETCH;   // (SLICED: s goes up by one here, so this is the pixel's last slice: lim == spp)
             } else if (F.pass == 1 && s >= F.pilot) {
                 save_pilot();
+                phase = FETCH;
+            } else if (SLICED && s >= lim) {
+                save_slice(cd);
                 phase = FETCH;
             } else {
                 tri = tc; j = 0;
@@ -491,7 +564,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     // of a pixel ends at sb + (k + 1) (spp - sb) / nsl)
     const unsigned nsl = (TS == 1 && F.slices > 1 && pass != 1) ? (unsigned)F.slices : 1u;
     const int sb = (ACC || pass == 2) ? F.pilot : 0;   // (ACC: the samples of earlier adds, rt_internal.h)
-    auto slice_end = [&](unsigned k) { return sb + (int)((k + 1u) * (unsigned)(spp - sb) / nsl); };
+    auto sl_end = [&](unsigned k) { return slice_end(sb, spp, nsl, k); };
     int lim = spp;
     // The deterministic prefix of the pixel's samples (FrameParams::fixed_point; BVH2 walk): a sample's
     // path up to its first diffuse or glossy bounce draws no random number -- it is the cached camera
@@ -527,28 +600,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
         F.pilot_cost[p] = s >= spp ? 0u : (unsigned)cost;
         if (!WIDE && F.pilot_draws) F.pilot_draws[p] = (uint32_t)ndraw;
     };
-    // slices: the pixel's state after this job's slice, stored write-through (sc1) for the lane that runs the
-    // next slice; then, once the wave's stores have completed, the samples done (the word that lane polls)
+    // slices: the pixel's state after this job's slice, for the lane that runs the next one (slice_publish)
     auto save_slice = [&]() __attribute__((always_inline)) {
         if (!team_leader) return;
-        gu64* st = (gu64*)(F.slice_state + 2 * (int64_t)p);
-        auto pk = [](float a, float b) { return (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32); };
-        __hip_atomic_store(st + 0, pk(acc.x, acc.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(st + 1, pk(acc.z, kc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(st + 2, (unsigned long long)seed0 | ((unsigned long long)seed1 << 32), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(st + 3, (unsigned long long)(unsigned)tc | ((unsigned long long)(unsigned)s << 32),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // The hand-off is built by hand, not as a release / acquire pair: at agent scope those compile on
-        // gfx950 to an L2 write-back (buffer_wbl2 sc1) before every ready store and an L2 invalidate
-        // (buffer_inv sc1) after every successful poll -- of the whole L2 the BVH lives in -- measured
-        // C3 106.9 -> 152.8 ms, C4 272.8 -> 297.1, C5 4,485 -> 5,705 ms (r06).  Here the
-        // state words and the count are sc1 (agent-scope) atomics, which write through to memory and
-        // read past this CU's L1; s_waitcnt vmcnt(0) orders the state stores' completion before the
-        // count store, and the reader's wavefront fence keeps its state loads after the poll.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store((gu32*)(F.slice_ready + p), (unsigned)s, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        slice_publish(F, (gu64*)(F.slice_state + 2 * (int64_t)p), p, acc, kc, seed0, seed1, (unsigned)tc, s);
     };
     auto finish_sample = [&]() __attribute__((always_inline)) {  // output += baseColor; next sample from the cached camera hit
         if (LOG && logme) log_event(F, 3.0f, s + 1, rtm_v3(0, 0, 0), rtm_v3(0, 0, 0), 0.0f, 0, so);
@@ -639,7 +694,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
                         tri = tc; j = 0;
                         so = rtm_v3(1, 1, 1);
                         drew = false;
-                        lim = slice_end(0);
+                        lim = sl_end(0);
                         phase = s >= spp ? FETCH : PREP;   // finished in pass 1: already written
                         if (nsl > 1 && s >= spp) save_slice();   // ... and its later slices have nothing to do
                     } else if (ACC && F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
@@ -653,10 +708,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
                         tri = tc; j = 0;
                         so = rtm_v3(1, 1, 1);
                         drew = false;
-                        lim = slice_end(0);
+                        lim = sl_end(0);
                         phase = PREP;
                     } else {
-                        lim = slice_end(0);
+                        lim = sl_end(0);
                         start(C.position, cd);
                     }
                 } else {
@@ -670,26 +725,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
         if (nsl > 1 && phase == WAIT_SLICE) {
             // slices: the previous slice's samples done, published by the lane that ran it (save_slice); its
             // state is read with sc1 loads (past this CU's L1) once the count is there
-            const unsigned need_s = (unsigned)slice_end((unsigned)lim - 1u);
-            const unsigned done_s = __hip_atomic_load((gu32*)(F.slice_ready + p), __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-            if (done_s >= need_s) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // the state loads stay after the poll
-                gu64* st = (gu64*)(F.slice_state + 2 * (int64_t)p);
-                const unsigned long long a = __hip_atomic_load(st + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long b = __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long d = __hip_atomic_load(st + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long e = __hip_atomic_load(st + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                acc = rtm_v3(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b));
-                kc = __uint_as_float((unsigned)(b >> 32));
-                seed0 = (uint32_t)d;
-                seed1 = (uint32_t)(d >> 32);
-                tc = (int)(unsigned)e;
-                s = (int)(unsigned)(e >> 32);
+            if (slice_ready(F, p, (unsigned)sl_end((unsigned)lim - 1u))) {
+                unsigned w;
+                slice_take((gu64*)(F.slice_state + 2 * (int64_t)p), acc, kc, seed0, seed1, w, s);
+                tc = (int)w;
                 tri = tc; j = 0;
                 so = rtm_v3(1, 1, 1);
                 drew = false;
-                lim = slice_end((unsigned)lim);
+                lim = sl_end((unsigned)lim);
                 phase = s >= spp ? FETCH : PREP;   // finished early (a sample that draws nothing): written
             }
         }
@@ -978,6 +1021,17 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     // blocks per CU for at most max_waves waves per SIMD (4 SIMDs per CU)
     const int cap_cu = fp.max_waves > 0 ? std::max(1, fp.max_waves * 4 * 64 / block) : INT_MAX;
     const int64_t resident = (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu, cap_cu));
+    // sample slices of the one-lane brute-force kernels (rt_api.hip setup_slices: fp.slices = K, or -K for K
+    // on auto, decided here where the resident lanes are known: rt_slices.h brute_slice_launch): one-pass
+    // launches only, and no teams -- a set slice count keeps a tile the team rule would take on single lanes.
+    // bslices: FrameParams::slices as the sliced kernels read it, K | tail << 8 (a set slice count slices every
+    // pixel, auto only the tile's last pixels), 0 for an unsliced launch
+    int bslices = 0;
+    if (BRUTE && !RESUME && fp.pass == 0 && fp.team <= 1 && fp.slice_state && fp.slice_ready && sc.ntri + 2 < 65536 &&
+        fp.npix <= INT_MAX)
+        bslices = brute_slice_launch(fp.slices, fp.nloc, resident * block);
+    constexpr int kBruteSl = BRUTE ? (kBruteClu | kBruteSliced) : 0;   // clustered or not, as above
+    constexpr int kBruteSl1 = BRUTE ? (1 | kBruteSliced) : 0;
     // team walk (render_resume_kernel TEAM): BVH2 item steps only; walk_team, 0 = auto (auto_walk_team;
     // pass 2 of a pilot launch: the size pilot_team_pick_kernel chose, launch_render)
     constexpr bool kTeamable = RESUME && STEP && !WIDE && !LOG;
@@ -994,6 +1048,7 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     f.team = 1;
     if (BRUTE) {
         f.team = fp.team;
+        if (bslices) f.team = 1;
         if (f.team == 0) {
             // measured on C2 tiles (one MI355X, 96-VGPR kernel: 327,680 resident lanes): a 1/8 tile
             // (131k pixels) is fastest with single lanes (2.23 vs 2.29 ms with pairs), a 1/16 tile with
@@ -1031,6 +1086,22 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
         if (e != hipSuccess) return e;
         grid = std::min(need, (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu_t, cap_cu)));
     }
+    // the sliced instantiations and their own occupancy: the grid stays within what the device keeps resident
+    // (not that the hand-off needs it: a job is only ever held by a wave that is running, and the job of a
+    // pixel's slice k is taken before that of its slice k + 1, so a waiting lane's chain ends in a running one)
+    const void* sfn = clu ? (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl, ACC>
+                          : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1, ACC>;
+    if (!RESUME) f.slices = bslices;
+    note_launch_slices(f.slices);   // (rt_debug_last_slices)
+    if (bslices) {
+        int per_cu_s = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, sfn, block, lds);
+        if (e != hipSuccess) return e;
+        grid = std::min(need, (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu_s, cap_cu)));
+        // the samples-done words of the tile's pixels (the tree walk's are zeroed by setup_slices)
+        e = hipMemsetAsync(f.slice_ready, 0, (size_t)fp.nloc * sizeof(uint32_t), stream);
+        if (e != hipSuccess) return e;
+    }
     e = hipMemsetAsync(d_work, 0, (size_t)kGroups * kCounterStride, stream);
     if (e != hipSuccess) return e;
     // the per-launch constants live after the counters in the same scratch block
@@ -1053,6 +1124,12 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     else if (RESUME)
         hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>), dim3((unsigned)grid), dim3(block), lds, stream,
                            sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
+    else if (BRUTE && bslices && clu)
+        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl, ACC>), dim3((unsigned)grid),
+                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
+    else if (BRUTE && bslices)
+        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1, ACC>), dim3((unsigned)grid),
+                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else if (BRUTE && f.team > 1)
         hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>), dim3((unsigned)grid),
                            dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
@@ -1110,6 +1187,11 @@ __global__ void __launch_bounds__(256) debug_trace_kernel(DevScene S, const floa
 // instantiations of the kernels (through launch_accum) and none of the other entry points, so the code
 // object of this one -- every one-shot kernel -- is built from exactly what it was built from without them
 #ifndef RT_ACCUM_TU
+// FrameParams::slices as the last launch's kernel got it (rt_debug_last_slices: which kernel a test launched)
+static std::atomic<int> g_last_slices{0};
+void note_launch_slices(int v) { g_last_slices.store(v, std::memory_order_relaxed); }
+int last_launch_slices() { return g_last_slices.load(std::memory_order_relaxed); }
+
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fn, x, y, out, n);

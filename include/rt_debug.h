@@ -105,6 +105,17 @@ int rt_debug_brute_clusters(const float* V_p, int64_t n_vp, const float* V_n, in
                             int layout, int cluster, float* slots, int64_t slot_cap, float* rows, int64_t row_cap,
                             int64_t info[4]);
 
+/* No device call: the rule for sample slices on a brute-force scene (option "slices" = option: -1 auto, 0 off,
+ * K) for a launch over a tile of nloc pixels on a device that keeps `lanes` lanes of the kernel resident, which
+ * brings every pixel to spp samples; accum_base >= 0: an add of a progressive accumulation that has accum_base of
+ * them already (-1: a one-shot frame).  out[0] = 1 when the launch takes slices, out[1] = K, out[2] = the share
+ * of the tile's pixels that are sliced, in 1/256 (the last ones handed out; 256 = every pixel), else all 0. */
+int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int accum_base, int32_t out[3]);
+
+/* What the kernel of the process's last render launch got as its slice word: 0 for an unsliced launch, K for the
+ * tree walk, K | share << 8 (as above) for a sliced brute-force launch. */
+int rt_debug_last_slices(void);
+
 #ifdef __cplusplus
 }
 #endif

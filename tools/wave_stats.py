@@ -37,6 +37,12 @@ for name in names:
                "trav_iters_per_wave_render_iter": round(c["wave_trav_iters"] / max(1, c["wave_render_iters"]), 2),
                "rays_per_lane_render_iter": round(c["rays"] / max(1, 64 * c["wave_render_iters"]), 4),
                "trav_cycle_share": round(c["cycles_trav"] / max(1, c["cycles_trav"] + c["cycles_shade"]), 4)}
+        if ctx.scene_info()["brute_records"] > 0:
+            # the brute-force loop: lanes holding a ray per box-loop round (its cost does not depend on them).
+            # On this path trav_simd_eff above is no efficiency: its numerator adds the triangle tests, which run
+            # in batches of their own outside the counted rounds, so it can exceed 1 (1.07 on C2 with slices);
+            # it is kept for comparison with the profiles of earlier rounds
+            out["brute_ray_fill"] = round(c["node_fetches"] / max(1, 64 * c["wave_trav_iters"]), 4)
         print(json.dumps(out), flush=True)
         if len(sys.argv) > 3:   # committed evidence (profiles/rNN_wave_stats.jsonl)
             with open(sys.argv[3], "a") as f:
