@@ -84,9 +84,82 @@ class Progressive(object):
         self._ctx.accum_read(out=out.reshape(-1))
         return out
 
+    # -- adaptive sampling: refine only the pixels that need it.  A pixel that has received n samples holds the
+    # value of ``launch_Raytracing`` at ``spp = n``, bit for bit, whatever the other pixels received. --
+    def _live(self) -> None:
+        if not self._open:
+            raise RuntimeError("the progressive render is closed (or was replaced by a later begin_progressive)")
+
+    def mark(self) -> None:
+        """Snapshot every pixel's sum and sample count: what ``select`` measures the frame's change against."""
+        self._live()
+        self._ctx.accum_mark()
+
+    def select(self, threshold: float) -> int:
+        """Select the pixels that got samples since ``mark`` and whose colour moved by more than ``threshold``
+        (|change| summed over r, g, b, over sqrt(r + g + b + 0.01) of the new colour; rt_api.h).  Returns how
+        many are selected."""
+        self._live()
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must not be NaN")
+        return self._ctx.accum_select(threshold)
+
+    def select_mask(self, mask) -> None:
+        """Select the pixels where ``mask`` (``imgDim`` elements, any shape) is non-zero."""
+        self._live()
+        m = np.asarray(mask)
+        if m.size != self._n:
+            raise ValueError(f"mask has {m.size} elements, needs imgDim = {self._n}")
+        self._ctx.accum_select_mask(m)
+
+    def select_all(self) -> None:
+        self._live()
+        self._ctx.accum_select_all()
+
+    def selection(self) -> np.ndarray:
+        """The current selection, a 0/1 uint8 mask of ``imgDim`` pixels."""
+        self._live()
+        return self._ctx.accum_selection()
+
+    def sample_map(self) -> np.ndarray:
+        """Samples done, pixel by pixel (int32 ``[imgDim]``)."""
+        self._live()
+        return self._ctx.accum_sample_map()
+
+    def add_selected(self, spp: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """``spp`` (>= 1) more samples of every selected pixel, each from its own count; the whole frame."""
+        out = self._out(out, np.float32)
+        self._ctx.accum_add_selected(int(spp), out=out.reshape(-1))
+        return out
+
+    def refine(self, threshold: float, min_spp: int, max_spp: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """On a fresh accumulation: ``2 * min_spp`` samples of every pixel, then doublings of only the pixels
+        whose colour still moved by more than ``threshold`` between the first half of their samples and all of
+        them (the half-buffer estimate), until none is left or they hold ``max_spp``.  A pixel ends with
+        ``2 * min_spp * 2**k`` samples (capped at ``max_spp``); returns the frame."""
+        min_spp, max_spp = int(min_spp), int(max_spp)
+        if min_spp < 1:
+            raise ValueError("min_spp must be >= 1")
+        if max_spp < 2 * min_spp:
+            raise ValueError("max_spp must be at least 2 * min_spp")
+        out = self._out(out, np.float32)
+        self.add(min_spp, out)
+        self.mark()
+        self.add(min_spp, out)
+        c = 2 * min_spp   # the samples every selected pixel holds
+        n = self.select(threshold)
+        while n > 0 and c < max_spp:
+            step = min(c, max_spp - c)
+            self.mark()
+            self.add_selected(step, out)
+            c += step
+            n = self.select(threshold)
+        return out
+
     @property
     def samples(self) -> int:
-        """Samples done per pixel (-1 once closed)."""
+        """Samples done per pixel -- the most a pixel holds once ``add_selected`` made them differ (-1 once closed)."""
         return self._ctx.accum_samples() if self._open else -1
 
     def close(self) -> None:

@@ -32,6 +32,9 @@ EXPORTED = (
     "rt_render_rgb8", "rt_rgb8_device", "rt_rgb8",
     "rt_accum_begin", "rt_accum_add", "rt_accum_add_rgb8", "rt_accum_read", "rt_accum_samples", "rt_accum_end",
     "rt_accum_begin_device", "rt_accum_add_device",
+    "rt_accum_mark", "rt_accum_select", "rt_accum_select_mask", "rt_accum_select_all", "rt_accum_selection",
+    "rt_accum_sample_map", "rt_accum_add_selected", "rt_accum_mark_device", "rt_accum_select_device",
+    "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
@@ -116,6 +119,18 @@ def lib():
             "rt_accum_end": (_i32, [_c_p]),
             "rt_accum_begin_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, _i32, _i32]),
             "rt_accum_add_device": (_i32, [_c_p, _i32, _i32, _c_p, _c_p]),
+            "rt_accum_mark": (_i32, [_c_p]),
+            "rt_accum_select": (_i32, [_c_p, ctypes.c_float, ctypes.POINTER(_i64)]),
+            "rt_accum_select_mask": (_i32, [_c_p, _c_p]),
+            "rt_accum_select_all": (_i32, [_c_p]),
+            "rt_accum_selection": (_i32, [_c_p, _c_p]),
+            "rt_accum_sample_map": (_i32, [_c_p, _c_p]),
+            "rt_accum_add_selected": (_i32, [_c_p, _i32, _c_p]),
+            "rt_accum_mark_device": (_i32, [_c_p, _i32, _c_p]),
+            "rt_accum_select_device": (_i32, [_c_p, _i32, ctypes.c_float, _c_p]),
+            "rt_accum_select_mask_device": (_i32, [_c_p, _i32, _c_p, _c_p]),
+            "rt_accum_select_all_device": (_i32, [_c_p, _i32, _c_p]),
+            "rt_accum_add_selected_device": (_i32, [_c_p, _i32, _i32, _c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -357,6 +372,67 @@ class Context:
     def accum_add_device(self, spp: int, d_out_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
         self._check(lib().rt_accum_add_device(self.handle, int(device_index), int(spp), _c_p(int(d_out_ptr)),
                                               _c_p(int(stream_ptr)) if stream_ptr else None))
+
+    # -- adaptive sampling (rt_accum_mark / rt_accum_select* / rt_accum_add_selected) --
+    def accum_mark(self) -> None:
+        self._check(lib().rt_accum_mark(self.handle))
+
+    def accum_select(self, threshold: float) -> int:
+        """Select the pixels whose error since the mark exceeds ``threshold``; returns how many."""
+        n = _i64(0)
+        self._check(lib().rt_accum_select(self.handle, ctypes.c_float(float(threshold)), ctypes.byref(n)))
+        return int(n.value)
+
+    def accum_select_mask(self, mask) -> None:
+        m = np.asarray(mask)
+        n = getattr(self, "_accum_npix", 0)
+        if m.size != n:
+            raise ValueError(f"mask has {m.size} elements, needs imgDim = {n}")
+        m = np.ascontiguousarray(m.reshape(-1) != 0, dtype=np.uint8)
+        self._check(lib().rt_accum_select_mask(self.handle, m.ctypes.data if m.size else None))
+
+    def accum_select_all(self) -> None:
+        self._check(lib().rt_accum_select_all(self.handle))
+
+    def accum_selection(self) -> np.ndarray:
+        """The current selection as a 0/1 uint8 mask of imgDim pixels."""
+        out = np.zeros(max(getattr(self, "_accum_npix", 0), 1), np.uint8)
+        self._check(lib().rt_accum_selection(self.handle, out.ctypes.data))
+        return out[:getattr(self, "_accum_npix", 0)]
+
+    def accum_sample_map(self) -> np.ndarray:
+        """Samples done, pixel by pixel (int32[imgDim])."""
+        out = np.zeros(max(getattr(self, "_accum_npix", 0), 1), np.int32)
+        self._check(lib().rt_accum_sample_map(self.handle, out.ctypes.data))
+        return out[:getattr(self, "_accum_npix", 0)]
+
+    def accum_add_selected(self, spp: int, out: np.ndarray = None) -> np.ndarray:
+        """``spp`` more samples of every selected pixel; returns the whole frame (float32[3*npix])."""
+        out = self._accum_out(out, np.float32)
+        self._check(lib().rt_accum_add_selected(self.handle, int(spp), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _stream(stream_ptr: int):
+        return _c_p(int(stream_ptr)) if stream_ptr else None
+
+    def accum_mark_device(self, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_mark_device(self.handle, int(device_index), self._stream(stream_ptr)))
+
+    def accum_select_device(self, threshold: float, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_select_device(self.handle, int(device_index), ctypes.c_float(float(threshold)),
+                                                 self._stream(stream_ptr)))
+
+    def accum_select_mask_device(self, d_mask_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_select_mask_device(self.handle, int(device_index), _c_p(int(d_mask_ptr)),
+                                                      self._stream(stream_ptr)))
+
+    def accum_select_all_device(self, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_select_all_device(self.handle, int(device_index), self._stream(stream_ptr)))
+
+    def accum_add_selected_device(self, spp: int, d_out_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_add_selected_device(self.handle, int(device_index), int(spp), _c_p(int(d_out_ptr)),
+                                                       self._stream(stream_ptr)))
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

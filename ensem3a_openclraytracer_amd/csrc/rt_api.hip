@@ -60,6 +60,16 @@ struct Device {
     float acc_cam[10] = {0}, acc_env[5] = {0};
     int64_t acc_npix = 0, acc_nloc = 0, acc_samples = 0;
     int acc_max_bounce = 0, acc_row0 = 0, acc_row_step = 1;
+    // Adaptive sampling (rt_accum_mark, rt_accum_select*, rt_accum_add_selected), each buffer allocated on first
+    // use: the snapshot (acc.xyz, s: 16 bytes per pixel); the selection (SelView: list, length, compaction
+    // scratch, 0/1 flags); and the list of every pixel, for a full add once the counts differ.  acc_samples is
+    // then the largest count a pixel can hold (full adds + every selected add), acc_full the full adds' samples.
+    DevBuf mark, sel, all;
+    bool acc_marked = false, acc_selected = false, acc_all_ready = false;
+    bool acc_uniform = true;      // every pixel holds acc_samples samples
+    bool sel_all = false;         // the selection is rt_accum_select_all's
+    int64_t sel_known = -1;       // the selection's length where the host knows it (the host forms), else -1
+    int64_t acc_full = 0;
     char* host_stage = nullptr;   // pinned staging for rt_render / rt_render_rgb8
     int* host_pick = nullptr;     // pinned: a two-pass launch's pass-2 pick, read back (rt::RenderPending)
     size_t host_stage_bytes = 0;
@@ -295,7 +305,11 @@ int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, i
 
 // rt_set_scene, rt_set_env and the options that redefine a hit: an open accumulation cannot be continued
 void invalidate_accum(rt_ctx* ctx) {
-    for (auto& d : ctx->devs) d.acc_valid = false;
+    for (auto& d : ctx->devs) {
+        d.acc_valid = false;
+        d.acc_marked = false;   // (mark and selection go with it)
+        d.acc_selected = false;
+    }
 }
 
 }  // namespace
@@ -349,7 +363,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.pending) (void)hipEventSynchronize(d.done);
         if (d.stream) (void)hipStreamSynchronize(d.stream);
         for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.brute_cbox, &d.brute_crow, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
-                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum})
+                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum, &d.mark, &d.sel, &d.all})
             release(*b);
         if (d.host_stage) (void)hipHostFree(d.host_stage);
         if (d.host_pick) (void)hipHostFree(d.host_pick);
@@ -880,14 +894,29 @@ int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t n
 }
 
 // ---- progressive accumulation (rt_accum_*) ----
+// begin and end: no mark, no selection, every pixel at the same count
+void accum_reset_selection(Device& d) {
+    d.acc_marked = false;
+    d.acc_selected = false;
+    d.acc_all_ready = false;
+    d.acc_uniform = true;
+    d.sel_all = false;
+    d.sel_known = -1;
+    d.acc_full = 0;
+}
+
 int accum_close_slot(rt_ctx* ctx, Device& d) {
     d.acc_open = false;
     d.acc_valid = false;
     d.acc_samples = 0;
-    if (!d.accum.p) return RT_OK;
+    accum_reset_selection(d);
+    if (!d.accum.p && !d.mark.p && !d.sel.p && !d.all.p) return RT_OK;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     if (d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));   // an add in flight still uses the state
     release(d.accum);
+    release(d.mark);
+    release(d.sel);
+    release(d.all);
     return RT_OK;
 }
 
@@ -909,15 +938,178 @@ int accum_check_add(rt_ctx* ctx, const Device& d, int spp) {
     return RT_OK;
 }
 
+// rt_accum_add_selected: the slot has a selection, every pixel at least one sample (a full add), and no
+// selected pixel would pass the limit -- compared against acc_samples, the most any pixel holds
+int accum_check_add_selected(rt_ctx* ctx, const Device& d, int spp) {
+    const char* what = "rt_accum_add_selected";
+    int st = accum_slot_usable(ctx, d, what);
+    if (st) return st;
+    if (!d.acc_selected) return set_err(ctx, RT_ERR_STATE, "%s: no selection (rt_accum_select*)", what);
+    if (d.acc_full < 1)
+        return set_err(ctx, RT_ERR_STATE, "%s: the accumulation has no full add yet (rt_accum_add)", what);
+    if (spp < 1) return set_err(ctx, RT_ERR_ARG, "%s: spp must be >= 1, got %d", what, spp);
+    if (d.acc_samples + (int64_t)spp > RT_ACCUM_MAX_SAMPLES)
+        return set_err(ctx, RT_ERR_ARG, "%s: %lld + %d samples exceed RT_ACCUM_MAX_SAMPLES (%d)", what,
+                       (long long)d.acc_samples, spp, (int)RT_ACCUM_MAX_SAMPLES);
+    return RT_OK;
+}
+
+// the selection's buffer (Device::sel) of a tile of n pixels: the list, its length, the compaction's scratch
+// (both device words), the 0/1 flags the list was compacted from (rt_accum_selection reads them back)
+struct SelView {
+    uint32_t* list;
+    uint32_t* count;
+    uint32_t* scratch;
+    uint8_t* flag;
+};
+size_t sel_bytes(int64_t n) { return (size_t)n * 4 + 4 + rt::select_scratch_words(n) * 4 + (size_t)n; }
+SelView sel_view(const Device& d) {
+    const size_t n = (size_t)d.acc_nloc;
+    char* b = (char*)d.sel.p;
+    return {(uint32_t*)b, (uint32_t*)(b + n * 4), (uint32_t*)(b + n * 4 + 4),
+            (uint8_t*)(b + n * 4 + 4 + rt::select_scratch_words(d.acc_nloc) * 4)};
+}
+
+// grow a per-slot buffer of the accumulation (growing frees the old one from the host: the last launch, on
+// any stream, may still use it)
+hipError_t accum_ensure(Device& d, DevBuf& b, size_t need) {
+    need = std::max<size_t>(need, 16);
+    if (b.bytes < need && d.pending) {
+        hipError_t e = hipEventSynchronize(d.done);
+        if (e != hipSuccess) return e;
+    }
+    return ensure(b, need);
+}
+
+// the slot's tile as check_frame describes it (row tiling, width, npix), for the select kernels
+void accum_tile(const Device& d, rt::FrameParams& fp) {
+    fp = rt::FrameParams{};
+    fp.width = (int32_t)d.acc_cam[6];
+    fp.npix = d.acc_npix;
+    fp.row0 = d.acc_row0;
+    fp.row_step = d.acc_row_step;
+    fp.nloc = d.acc_nloc;
+}
+
+int accum_slot_of(rt_ctx* ctx, int device_index, const char* what, Device** out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    Device& d = ctx->devs[device_index];
+    const int st = accum_slot_usable(ctx, d, what);
+    if (st) return st;
+    if (d.acc_samples == 0) return set_err(ctx, RT_ERR_STATE, "%s: the accumulation has no samples yet", what);
+    *out = &d;
+    return RT_OK;
+}
+
+// flags -> the ordered list (what: 0 the error measure against the mark, 1 a tile-packed device mask, 2 all)
+int accum_select_slot(rt_ctx* ctx, Device& d, int what, float threshold, const uint8_t* d_mask, hipStream_t s) {
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, accum_ensure(d, d.sel, sel_bytes(d.acc_nloc)));
+    const SelView v = sel_view(d);
+    rt::FrameParams fp;
+    accum_tile(d, fp);
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    d.acc_selected = false;   // (an error below leaves the list undefined)
+    if (what == 0)
+        HIP_OR_RET(ctx, rt::launch_select_error((const float4*)d.accum.p, (const float4*)d.mark.p, v.flag, fp, threshold, s));
+    else
+        HIP_OR_RET(ctx, rt::launch_select_mask(what == 1 ? d_mask : nullptr, v.flag, fp, s));
+    HIP_OR_RET(ctx, rt::launch_select_compact(v.flag, d.acc_nloc, v.scratch, v.list, v.count, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    d.acc_selected = true;
+    d.sel_all = what == 2;
+    d.sel_known = -1;
+    return RT_OK;
+}
+
+// the host forms of the selects: every slot's select on its own stream, then the lengths read back
+int accum_select_host(rt_ctx* ctx, int what, float threshold, const uint8_t* mask, int64_t* n_selected,
+                      const char* name) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", name);
+    if (what == 1 && !mask) return set_err(ctx, RT_ERR_ARG, "%s: mask must not be NULL", name);
+    const int nd = (int)ctx->devs.size();
+    for (int k = 0; k < nd; ++k) {
+        Device* d = nullptr;
+        const int st = accum_slot_of(ctx, k, name, &d);
+        if (st) return st;
+        if (what == 0 && !d->acc_marked) return set_err(ctx, RT_ERR_STATE, "%s: no mark (rt_accum_mark)", name);
+    }
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    std::vector<std::vector<uint8_t>> tiles(nd);   // (kept until the copies are done)
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        const uint8_t* d_mask = nullptr;
+        if (what == 1 && d.acc_nloc > 0) {   // the slot's rows of the mask, tile-packed, staged in d.out8
+            tiles[k].assign((size_t)d.acc_nloc, 0);
+            const int64_t rows = rt_tile_rows(npix, W, k, nd);
+            for (int64_t r = 0; r < rows; ++r) {
+                const int64_t first = ((int64_t)k + r * nd) * W;
+                std::memcpy(tiles[k].data() + r * W, mask + first, (size_t)std::min<int64_t>(W, npix - first));
+            }
+            HIP_OR_RET(ctx, accum_ensure(d, d.out8, (size_t)d.acc_nloc));
+            HIP_OR_RET(ctx, order_after_last(d, d.stream));
+            HIP_OR_RET(ctx, hipMemcpyAsync(d.out8.p, tiles[k].data(), (size_t)d.acc_nloc, hipMemcpyHostToDevice, d.stream));
+            d_mask = (const uint8_t*)d.out8.p;
+        }
+        const int st = accum_select_slot(ctx, d, what, threshold, d_mask, d.stream);
+        if (st) return st;
+    }
+    int64_t total = 0;
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        uint32_t n = 0;
+        HIP_OR_RET(ctx, hipMemcpyAsync(&n, sel_view(d).count, sizeof n, hipMemcpyDeviceToHost, d.stream));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+        d.sel_known = n;
+        total += n;
+    }
+    if (n_selected) *n_selected = total;
+    return RT_OK;
+}
+
+// a per-pixel array of every slot (elem bytes per pixel, tile-packed at src(d)) gathered into the frame's order
+int accum_gather_host(rt_ctx* ctx, void* out, size_t elem, const void* (*src)(Device&)) {
+    const int nd = (int)ctx->devs.size();
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    std::vector<char> tile;
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        if (d.acc_nloc <= 0) continue;
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        tile.resize((size_t)d.acc_nloc * elem);
+        HIP_OR_RET(ctx, order_after_last(d, d.stream));
+        HIP_OR_RET(ctx, hipMemcpyAsync(tile.data(), src(d), tile.size(), hipMemcpyDeviceToHost, d.stream));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+        const int64_t rows = rt_tile_rows(npix, W, k, nd);
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t first = ((int64_t)k + r * nd) * W;
+            std::memcpy((char*)out + first * elem, tile.data() + r * W * elem,
+                        (size_t)std::min<int64_t>(W, npix - first) * elem);
+        }
+    }
+    return RT_OK;
+}
+
 // the host forms: add spp samples on every slot (read: resolve the state instead, nothing rendered), then read
 // the frame back as render_host_ does (rgb8 >= 0: quantised on the devices first); out may be NULL for an add
-int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char* what) {
+// (selected: rt_accum_add_selected -- the add runs on each slot's selection)
+int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char* what, bool selected = false) {
     if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
     if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
         return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
     const int nd = (int)ctx->devs.size();
     for (int k = 0; k < nd; ++k) {
-        const int st = read ? accum_slot_usable(ctx, ctx->devs[k], what) : accum_check_add(ctx, ctx->devs[k], spp);
+        const int st = read       ? accum_slot_usable(ctx, ctx->devs[k], what)
+                       : selected ? accum_check_add_selected(ctx, ctx->devs[k], spp)
+                                  : accum_check_add(ctx, ctx->devs[k], spp);
         if (st) return st;
     }
     if (read && ctx->devs[0].acc_samples == 0)
@@ -940,7 +1132,8 @@ int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char*
             d.host_stage_bytes = bytes;
         }
         if (!read) {
-            const int st = rt_accum_add_device(ctx, k, spp, (float*)d.out.p, d.stream);
+            const int st = selected ? rt_accum_add_selected_device(ctx, k, spp, (float*)d.out.p, d.stream)
+                                    : rt_accum_add_device(ctx, k, spp, (float*)d.out.p, d.stream);
             if (st) return st;
         } else if (d.acc_nloc > 0) {
             HIP_OR_RET(ctx, order_after_last(d, d.stream));
@@ -1002,6 +1195,7 @@ int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], co
     d.acc_row0 = row0;
     d.acc_row_step = row_step;
     d.acc_samples = 0;
+    accum_reset_selection(d);
     d.acc_open = true;
     d.acc_valid = true;
     ctx->accum_host = false;
@@ -1024,9 +1218,28 @@ int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, vo
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, order_after_last(d, s));
+    if (!d.acc_uniform && fp.nloc > 0) {
+        // the pixels' counts differ (rt_accum_add_selected): the listed kernel over every pixel, each from its own
+        // count, then the frame resolved from the state (pixel by pixel the divisor differs)
+        HIP_OR_RET(ctx, accum_ensure(d, d.all, (size_t)fp.nloc * 4 + 4));
+        uint32_t* all = (uint32_t*)d.all.p;
+        if (!d.acc_all_ready) HIP_OR_RET(ctx, rt::launch_list_all(all, fp.nloc, all + fp.nloc, s));
+        d.acc_all_ready = true;
+        fp.spp = spp;
+        d.acc_valid = false;
+        HIP_OR_RET(ctx, rt::launch_accum_listed(dev_scene(ctx, d), fp, (float4*)d.accum.p, all, all + fp.nloc,
+                                                effective_traversal(ctx), ctx->block, d_out, (unsigned int*)d.work.p, s));
+        HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, d_out, fp.nloc, s));
+        HIP_OR_RET(ctx, mark_launch(d, s));
+        d.acc_valid = true;
+        d.acc_samples += spp;
+        d.acc_full += spp;
+        return RT_OK;
+    }
     // an add is one pass: no pilot pass and no trails (whatever "pilot" and "spec" say); sample slices as
     // rt_render_device would take them, over the samples this add runs
     HIP_OR_RET(ctx, setup_slices(ctx, d, fp, s, (int)d.acc_samples));
+    d.acc_full += spp;
     if (fp.nloc > 0) {
         d.acc_valid = false;   // (an error below leaves the state undefined)
         HIP_OR_RET(ctx, rt::launch_accum(dev_scene(ctx, d), fp, (float4*)d.accum.p, (int)d.acc_samples,
@@ -1079,6 +1292,136 @@ int rt_accum_end(rt_ctx* ctx) {
     }
     ctx->accum_host = false;
     return rc;
+}
+
+// ---- adaptive sampling: mark, select, add to the selection ----
+int rt_accum_mark_device(rt_ctx* ctx, int device_index, void* stream) {
+    Device* dp = nullptr;
+    const int st = accum_slot_of(ctx, device_index, "rt_accum_mark", &dp);
+    if (st) return st;
+    Device& d = *dp;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, accum_ensure(d, d.mark, (size_t)d.acc_nloc * sizeof(float4)));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    d.acc_marked = false;
+    HIP_OR_RET(ctx, rt::launch_accum_mark((const float4*)d.accum.p, (float4*)d.mark.p, d.acc_nloc, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    d.acc_marked = true;
+    return RT_OK;
+}
+
+int rt_accum_select_device(rt_ctx* ctx, int device_index, float threshold, void* stream) {
+    Device* dp = nullptr;
+    const int st = accum_slot_of(ctx, device_index, "rt_accum_select", &dp);
+    if (st) return st;
+    if (!dp->acc_marked) return set_err(ctx, RT_ERR_STATE, "rt_accum_select: no mark (rt_accum_mark)");
+    return accum_select_slot(ctx, *dp, 0, threshold, nullptr, (hipStream_t)stream);
+}
+
+int rt_accum_select_mask_device(rt_ctx* ctx, int device_index, const uint8_t* d_mask, void* stream) {
+    Device* dp = nullptr;
+    const int st = accum_slot_of(ctx, device_index, "rt_accum_select_mask", &dp);
+    if (st) return st;
+    if (!d_mask && dp->acc_nloc > 0) return set_err(ctx, RT_ERR_ARG, "rt_accum_select_mask: d_mask must not be NULL");
+    return accum_select_slot(ctx, *dp, 1, 0.0f, d_mask, (hipStream_t)stream);
+}
+
+int rt_accum_select_all_device(rt_ctx* ctx, int device_index, void* stream) {
+    Device* dp = nullptr;
+    const int st = accum_slot_of(ctx, device_index, "rt_accum_select_all", &dp);
+    if (st) return st;
+    return accum_select_slot(ctx, *dp, 2, 0.0f, nullptr, (hipStream_t)stream);
+}
+
+int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    Device& d = ctx->devs[device_index];
+    int st = accum_check_add_selected(ctx, d, spp);
+    if (st) return st;
+    rt::FrameParams fp;
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, spp, d.acc_row0, d.acc_row_step, &fp);
+    if (st) return st;
+    if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
+    fp.max_bounce = d.acc_max_bounce;
+    if (fp.nloc <= 0) return RT_OK;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    if (d.sel_known != 0) {   // (a selection the host knows to be empty adds nothing)
+        const SelView v = sel_view(d);
+        d.acc_valid = false;   // (an error below leaves the state undefined)
+        HIP_OR_RET(ctx, rt::launch_accum_listed(dev_scene(ctx, d), fp, (float4*)d.accum.p, v.list, v.count,
+                                                effective_traversal(ctx), ctx->block, d_out, (unsigned int*)d.work.p, s));
+        d.acc_valid = true;
+        d.acc_samples += spp;
+        if (!(d.sel_all && d.acc_uniform)) d.acc_uniform = false;
+        else d.acc_full += spp;   // (every pixel, all at one count: a full add by another name)
+    }
+    // the whole frame, every pixel at its own count (the kernel wrote the listed pixels only)
+    HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, d_out, d.acc_nloc, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int rt_accum_mark(rt_ctx* ctx) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "rt_accum_mark: no accumulation is open (rt_accum_begin)");
+    for (int k = 0; k < (int)ctx->devs.size(); ++k) {
+        const int st = rt_accum_mark_device(ctx, k, ctx->devs[k].stream);
+        if (st) return st;
+    }
+    return RT_OK;
+}
+
+int rt_accum_select(rt_ctx* ctx, float threshold, int64_t* n_selected) {
+    return accum_select_host(ctx, 0, threshold, nullptr, n_selected, "rt_accum_select");
+}
+
+int rt_accum_select_mask(rt_ctx* ctx, const uint8_t* mask) {
+    return accum_select_host(ctx, 1, 0.0f, mask, nullptr, "rt_accum_select_mask");
+}
+
+int rt_accum_select_all(rt_ctx* ctx) { return accum_select_host(ctx, 2, 0.0f, nullptr, nullptr, "rt_accum_select_all"); }
+
+int rt_accum_selection(rt_ctx* ctx, uint8_t* mask_out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "rt_accum_selection: no accumulation is open (rt_accum_begin)");
+    if (!mask_out) return set_err(ctx, RT_ERR_ARG, "mask_out must not be NULL");
+    for (const auto& d : ctx->devs) {
+        const int st = accum_slot_usable(ctx, d, "rt_accum_selection");
+        if (st) return st;
+        if (!d.acc_selected) return set_err(ctx, RT_ERR_STATE, "rt_accum_selection: no selection (rt_accum_select*)");
+    }
+    return accum_gather_host(ctx, mask_out, 1, [](Device& d) { return (const void*)sel_view(d).flag; });
+}
+
+int rt_accum_sample_map(rt_ctx* ctx, int32_t* out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "rt_accum_sample_map: no accumulation is open (rt_accum_begin)");
+    if (!out) return set_err(ctx, RT_ERR_ARG, "out must not be NULL");
+    for (int k = 0; k < (int)ctx->devs.size(); ++k) {
+        Device* dp = nullptr;
+        const int st = accum_slot_of(ctx, k, "rt_accum_sample_map", &dp);
+        if (st) return st;
+    }
+    for (auto& d : ctx->devs) {   // the counts out of the state, staged in d.out
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, accum_ensure(d, d.out, (size_t)d.acc_nloc * sizeof(int32_t)));
+        HIP_OR_RET(ctx, order_after_last(d, d.stream));
+        HIP_OR_RET(ctx, rt::launch_sample_map((const float4*)d.accum.p, (int32_t*)d.out.p, d.acc_nloc, d.stream));
+        HIP_OR_RET(ctx, mark_launch(d, d.stream));
+    }
+    return accum_gather_host(ctx, out, sizeof(int32_t), [](Device& d) { return (const void*)d.out.p; });
+}
+
+int rt_accum_add_selected(rt_ctx* ctx, int spp, float* out_rgb) {
+    return accum_host(ctx, spp, false, out_rgb, -1, "rt_accum_add_selected", true);
 }
 
 int rt_render(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,

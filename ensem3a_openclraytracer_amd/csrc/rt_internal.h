@@ -187,6 +187,32 @@ hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, fl
 // slices as set in fp; no pilot pass, no trails).
 hipError_t launch_accum(const DevScene& sc, const FrameParams& fp, float4* state, int base, int traversal, int block,
                         float* d_out, unsigned int* d_work, hipStream_t stream);
+// A listed add (rt_accum_add_selected): the kAccListed instantiations, which read two more pilot fields in a
+// meaning of their own -- pilot_order is the list of tile pixels to refine (ascending), pilot_cost points at its
+// length, a device word the kernel only reads -- and fp.spp is the samples the add gives each listed pixel, on
+// top of the count s its state holds (pilot is 0 and unused).  One pass, no slices; one lane per pixel unless
+// fp.team / fp.walk_team are set.  out receives clamp(acc / s) of the listed pixels only.
+hipError_t launch_accum_listed(const DevScene& sc, const FrameParams& fp, float4* state, const uint32_t* list,
+                               const uint32_t* count, int traversal, int block, float* d_out, unsigned int* d_work,
+                               hipStream_t stream);
+// Adaptive sampling's selection (rt_accum_mark / rt_accum_select*; kernels in rt_adaptive.hip's translation unit):
+//   launch_accum_mark      mark[p] = (acc.xyz, s) of the n pixels of a state;
+//   launch_select_error    flag[p] = 1 where the pixel got samples since the mark and its error exceeds the
+//                          threshold (rt_api.h), else 0; padding pixels of a partial last row 0;
+//   launch_select_mask     flag[p] = src[p] != 0 (src NULL: 1), padding pixels 0; src is tile-packed, on the device;
+//   launch_select_compact  list = the flagged tile pixels in ascending order, *count = how many; scratch:
+//                          select_scratch_words(n) words;
+//   launch_list_all        list = 0 .. n - 1, *count = n;
+//   launch_sample_map      out[p] = s of the n pixels of a state.
+size_t select_scratch_words(int64_t n);
+hipError_t launch_accum_mark(const float4* state, float4* mark, int64_t n, hipStream_t stream);
+hipError_t launch_select_error(const float4* state, const float4* mark, uint8_t* flag, const FrameParams& fp,
+                               float threshold, hipStream_t stream);
+hipError_t launch_select_mask(const uint8_t* src, uint8_t* flag, const FrameParams& fp, hipStream_t stream);
+hipError_t launch_select_compact(const uint8_t* flag, int64_t n, uint32_t* scratch, uint32_t* list, uint32_t* count,
+                                 hipStream_t stream);
+hipError_t launch_list_all(uint32_t* list, int64_t n, uint32_t* count, hipStream_t stream);
+hipError_t launch_sample_map(const float4* state, int32_t* out, int64_t n, hipStream_t stream);
 // out[3 p ..] = clamp(acc / s) of the n pixels of an accumulation state (rt_accum_read)
 hipError_t launch_accum_resolve(const float4* state, float* d_out, int64_t n, hipStream_t stream);
 hipError_t launch_prep_frames(const DevScene& sc, float4* frame, hipStream_t stream);

@@ -49,12 +49,17 @@ __device__ __forceinline__ void save_state(float4* __restrict__ st, int p, rtm_f
 // lane traces exactly one ray (primary, bounce or sun ray).
 // ACC: an add of a progressive accumulation (rt_internal.h: F.pilot_state its state, F.pilot the samples done,
 // one pass) -- instantiations of their own, so that
-// the one-shot kernels keep their code and registers
+// the one-shot kernels keep their code and registers.  kAccAdd: every pixel of the tile, from the uniform base
+// F.pilot to F.spp.  kAccListed (rt_accum_add_selected; compiled in rt_adaptive.hip's translation unit only): the
+// pixels of a list (F.pilot_order; its length a device word, F.pilot_cost), each from the count s its state
+// holds to s + F.spp -- base and limit are per lane (slimit below)
+[[maybe_unused]] constexpr int kAccAdd = 1;
+constexpr int kAccListed = 2;
 // BRUTE_: the brute-force loop (0 none, 1 lock-step, 2 teams, 3 clustered), + kBruteSliced for the launches
 // that hand out sample slices (FrameParams::slices; one lane per pixel: 1 and 3 only) -- instantiations of
 // their own again, so that an unsliced launch runs the code it ran without them
 constexpr int kBruteSliced = 4;
-template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, bool ACC = false>
+template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, int ACC = 0>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
 // spills, the instrumented (COUNT) ones spill a few registers to scratch.
@@ -124,7 +129,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     const int imgSize = (int)F.npix;
     const float e3 = F.env[3], e4 = F.env[4];
     const int spp = F.spp, maxB = F.max_bounce;
-    const unsigned int nloc = (unsigned int)F.nloc;
+    // (a listed add hands out the list's entries: its length is read once, and made wave-uniform for the hand-out)
+    const unsigned int nloc = ACC == kAccListed ? (unsigned int)__builtin_amdgcn_readfirstlane((int)*F.pilot_cost)
+                                                : (unsigned int)F.nloc;
     const int lane = threadIdx.x & 63;
     const int ts = BRUTE == 2 ? F.team : 1;                      // lanes per pixel (1, 2, 4, 8)
     const int team_lane0 = lane & ~(ts - 1);
@@ -134,7 +141,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
 
     int phase = FETCH;
     PixelQueue pq;
-    pq.per = (F.handout && F.pass != 2) ? (unsigned)((F.nloc + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
+    pq.per = (F.handout && F.pass != 2) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
     int p = 0, i = 0;
     bool logme = false;
     uint32_t seed0 = 0, seed1 = 0;
@@ -149,6 +156,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     rtm_f3 Bo = rtm_v3(0, 0, 0), Bd = rtm_v3(0, 0, 0);
     rtm_f3 acc = rtm_v3(0, 0, 0);
     int s = 0;
+    // the sample count the pixel stops at: F.spp, or in a listed add the pixel's own (the s it restored + F.spp).
+    // (A named lambda with the choice in an if constexpr: of the forms tried, the one that leaves the other
+    // instantiations' code as it was)
+    [[maybe_unused]] int plim = 0;
+    auto slimit = [&]() __attribute__((always_inline)) { if constexpr (ACC == kAccListed) return plim; else return spp; };
     int cost = 0;   // pass 1: rays this pixel traced (pilot_cost)
     int sun0 = -2;  // the first bounce's shadow-ray hit (-1 = miss; -2 = not traced yet)
     unsigned long long t_prev = 0;   // COUNT: the wave clock at the previous loop head
@@ -209,7 +221,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 const bool whole = !SLICED || sl == kWholeJob;
                 bool ok = q < nloc;
                 if (ok) {
-                    p = F.pass == 2 ? (int)F.pilot_order[q] : (int)q;
+                    p = (ACC == kAccListed || F.pass == 2) ? (int)F.pilot_order[q] : (int)q;
                     const int krow = p / W;
                     const int col = p - krow * W;
                     const int64_t i64 = ((int64_t)F.row0 + (int64_t)krow * F.row_step) * W + col;
@@ -243,7 +255,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                         so = rtm_v3(1, 1, 1);
                         phase = s >= spp ? FETCH : PREP;   // finished in pass 1: already written
                     }
-                    if constexpr (ACC) if (F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
+                    if constexpr (ACC) if (ACC == kAccListed || F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
                         const float4 a = F.pilot_state[2 * (int64_t)p], b = F.pilot_state[2 * (int64_t)p + 1];
                         acc = rtm_v3(a.x, a.y, a.z);
                         kc = a.w;
@@ -254,6 +266,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                         tri = tc; j = 0;
                         so = rtm_v3(1, 1, 1);
                         phase = PREP;
+                        if constexpr (ACC == kAccListed) plim = s + spp;
                     }
                     if constexpr (SLICED) lim = whole ? spp : send(0);
                 } else {
@@ -341,12 +354,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 // sample again (same cached camera hit, same state): their colours are added in order,
                 // bit for bit the reference's sum (FrameParams::fixed_point).
                 if (TRAV == TRAV_FAST && F.fixed_point && j == 0 && !(LOG && logme)) {
-                    if (COUNT) c.samples += (unsigned long long)max(spp - s, 0);
-                    for (; s < spp; ++s) acc = rtm_add(acc, so);
+                    if (COUNT) c.samples += (unsigned long long)max(slimit() - s, 0);
+                    for (; s < slimit(); ++s) acc = rtm_add(acc, so);
                 }
-                if (s >= spp) {
+                if (s >= slimit()) {
                     phase = FETCH;
-                    if (team_leader) store_pixel(out, p, acc, spp);
+                    if (team_leader) store_pixel(out, p, acc, slimit());
                     if (F.pass == 1) save_pilot();
                     if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                     if constexpr (SLICED) { if (lim < spp) save_slice(cd); }   // done early: its later slices find nothing to do
@@ -441,8 +454,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             acc = rtm_add(acc, so);
             if (COUNT) c.samples++;
             ++s;
-            if (s >= spp) {
-                if (team_leader) store_pixel(out, p, acc, spp);
+            if (s >= slimit()) {
+                if (team_leader) store_pixel(out, p, acc, slimit());
                 if (F.pass == 1) save_pilot();
                 if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                 phase = FETCH;   // (SLICED: s goes up by one here, so this is the pixel's last slice: lim == spp)
@@ -492,7 +505,7 @@ constexpr size_t kStepMaxBytes = 16u << 20;
 // TS > 1: teams of TS lanes per pixel walk each ray together (team_step; BVH2 item steps only).
 // WIDE: 0 = the BVH2 walk, 1 = the 4-wide walk, 2 = the 4-wide walk with origin-folded dequantisation
 // (wide_node DQ; launch_fast picks it when the camera lies within DevScene::wdq_omax)
-template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS = 1, bool ACC = false>
+template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS = 1, int ACC = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? kWideWaves : 4))) render_resume_kernel(DevScene S, FrameParams F, float* __restrict__ out,
                                                       unsigned long long* __restrict__ counts,
                                                       unsigned int* __restrict__ work_counter,
@@ -526,7 +539,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     const int imgSize = (int)F.npix;
     const float e3 = F.env[3], e4 = F.env[4];
     const int spp = F.spp, maxB = F.max_bounce;
-    const unsigned int nloc = (unsigned int)F.nloc;
+    // (a listed add hands out the list's entries: its length is read once, and made wave-uniform for the hand-out)
+    const unsigned int nloc = ACC == kAccListed ? (unsigned int)__builtin_amdgcn_readfirstlane((int)*F.pilot_cost)
+                                                : (unsigned int)F.nloc;
     const int lane = threadIdx.x & 63;
     static_assert(TS == 1 || ((TS == 2 || TS == 4 || TS == 8) && STEP && !WIDE), "team walk: BVH2 item steps");
     const int team_lane0 = lane & ~(TS - 1);
@@ -538,7 +553,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     int phase = FETCH;
     bool tracing = false;
     PixelQueue pq;
-    pq.per = (F.handout && pass != 2) ? (unsigned)((F.nloc + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
+    pq.per = (F.handout && pass != 2) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
     FastRay T;
     T.item = 0; T.soff = 0; T.bk = 1000.0f; T.bt = -1; T.brank = -1; T.any = false;
     T.o = rtm_v3(0, 0, 0); T.d = rtm_v3(0, 0, 1); T.ix = T.iy = T.iz = 0.0f;
@@ -562,10 +577,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     // slice before it (phase WAIT_SLICE), the job's slice index
     // (one-pass launches, and pass 2 of a pilot launch: the samples after the pilot's sb = F.pilot; slice k
     // of a pixel ends at sb + (k + 1) (spp - sb) / nsl)
-    const unsigned nsl = (TS == 1 && F.slices > 1 && pass != 1) ? (unsigned)F.slices : 1u;
+    const unsigned nsl = (ACC != kAccListed && TS == 1 && F.slices > 1 && pass != 1) ? (unsigned)F.slices : 1u;   // (a listed add takes none)
     const int sb = (ACC || pass == 2) ? F.pilot : 0;   // (ACC: the samples of earlier adds, rt_internal.h)
     auto sl_end = [&](unsigned k) { return slice_end(sb, spp, nsl, k); };
     int lim = spp;
+    // the sample count the pixel stops at: F.spp, or in a listed add the pixel's own (the s it restored + F.spp).
+    // (A named lambda with the choice in an if constexpr: of the forms tried, the one that leaves the other
+    // instantiations' code as it was)
+    [[maybe_unused]] int plim = 0;
+    auto slimit = [&]() __attribute__((always_inline)) { if constexpr (ACC == kAccListed) return plim; else return spp; };
     // The deterministic prefix of the pixel's samples (FrameParams::fixed_point; BVH2 walk): a sample's
     // path up to its first diffuse or glossy bounce draws no random number -- it is the cached camera
     // hit followed by straight-through glass bounces (Raytracing.cl:72-77) -- so it is the same path in
@@ -586,7 +606,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     bool fdb = false;          // the bounce in flight is the sample's first drawing bounce
 
     auto write_pixel = [&]() __attribute__((always_inline)) {
-        if (team_leader) store_pixel(out, p, acc, spp);
+        if (team_leader) store_pixel(out, p, acc, slimit());
         // ACC: the pixel's last sample of this add: its state for the next add
         if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
     };
@@ -610,8 +630,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
         acc = rtm_add(acc, so);
         if (COUNT) c.samples++;
         ++s;
-        if (s >= spp) write_pixel();
-        const bool stop = (pass == 1 && (s >= spp || s >= F.pilot)) || (nsl > 1 && s >= lim);
+        if (s >= slimit()) write_pixel();
+        const bool stop = (pass == 1 && (s >= slimit() || s >= F.pilot)) || (nsl > 1 && s >= lim);
         if (stop) {
             if (nsl > 1) save_slice();
             else save_pilot();
@@ -619,7 +639,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
         // the next sample restarts from the cached camera hit; written as selects so that no branch
         // ends in a store the compiler could merge with the pixel store (that would force the path
         // state into scratch memory through a generic pointer)
-        phase = (s >= spp || stop) ? FETCH : PREP;
+        phase = (s >= slimit() || stop) ? FETCH : PREP;
         tri = tc; j = 0;
         so = rtm_v3(1, 1, 1);
         drew = false;
@@ -635,8 +655,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
     // reference's sum (FrameParams::fixed_point).
     auto repeat_fixed = [&]() __attribute__((always_inline)) {
         if (F.fixed_point && !drew && !(LOG && logme)) {
-            if (COUNT) c.samples += (unsigned long long)max(spp - 1 - s, 0);
-            for (; s + 1 < spp; ++s) acc = rtm_add(acc, so);
+            if (COUNT) c.samples += (unsigned long long)max(slimit() - 1 - s, 0);
+            for (; s + 1 < slimit(); ++s) acc = rtm_add(acc, so);
         }
     };
     auto start = [&](rtm_f3 o, rtm_f3 d) __attribute__((always_inline)) {
@@ -657,11 +677,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
         if (need) {
             const unsigned int qj = take_pixel(pq, need, team_lane0, work_counter, nloc, lane, nsl);
             if (phase == FETCH) {
-                const unsigned sl = qj / nloc;   // the job's slice (>= nsl: none left)
+                const unsigned sl = ACC == kAccListed ? 0u : qj / nloc;   // the job's slice (>= nsl: none left; a listed add has none)
                 const unsigned q = sl < nsl ? qj - sl * nloc : nloc;
                 bool ok = q < nloc;
                 if (ok) {
-                    p = pass == 2 ? (int)F.pilot_order[q] : (int)q;
+                    p = (ACC == kAccListed || pass == 2) ? (int)F.pilot_order[q] : (int)q;
                     const int krow = p / W;
                     const int col = p - krow * W;
                     const int64_t i64 = ((int64_t)F.row0 + (int64_t)krow * F.row_step) * W + col;
@@ -697,7 +717,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
                         lim = sl_end(0);
                         phase = s >= spp ? FETCH : PREP;   // finished in pass 1: already written
                         if (nsl > 1 && s >= spp) save_slice();   // ... and its later slices have nothing to do
-                    } else if (ACC && F.pilot > 0) {   // continue the accumulation: camera hit cached, sample s next
+                    } else if (ACC == kAccListed || (ACC && F.pilot > 0)) {   // continue the accumulation: camera hit cached, sample s next
                         const float4 a = F.pilot_state[2 * (int64_t)p], b = F.pilot_state[2 * (int64_t)p + 1];
                         acc = rtm_v3(a.x, a.y, a.z);
                         kc = a.w;
@@ -710,6 +730,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ?
                         drew = false;
                         lim = sl_end(0);
                         phase = PREP;
+                        if constexpr (ACC == kAccListed) plim = s + spp;
                     } else {
                         lim = sl_end(0);
                         start(C.position, cd);
@@ -983,7 +1004,7 @@ __global__ void pilot_team_pick_kernel(const unsigned* __restrict__ left, int64_
 }
 
 template <int TRAV, bool COUNT, bool LOG, bool SMEM = false, bool RESUME = false, bool OVF = false,
-          bool BRUTE = false, bool STEP = true, int WIDE = 0, bool ACC = false>
+          bool BRUTE = false, bool STEP = true, int WIDE = 0, int ACC = 0>
 hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float* d_out, unsigned long long* d_counts,
                     unsigned int* d_work, hipStream_t stream) {
     // FAST: int2 entries; the brute-force path of small scenes needs no stack
@@ -1027,7 +1048,7 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     // bslices: FrameParams::slices as the sliced kernels read it, K | tail << 8 (a set slice count slices every
     // pixel, auto only the tile's last pixels), 0 for an unsliced launch
     int bslices = 0;
-    if (BRUTE && !RESUME && fp.pass == 0 && fp.team <= 1 && fp.slice_state && fp.slice_ready && sc.ntri + 2 < 65536 &&
+    if (BRUTE && !RESUME && ACC != kAccListed && fp.pass == 0 && fp.team <= 1 && fp.slice_state && fp.slice_ready && sc.ntri + 2 < 65536 &&
         fp.npix <= INT_MAX)
         bslices = brute_slice_launch(fp.slices, fp.nloc, resident * block);
     constexpr int kBruteSl = BRUTE ? (kBruteClu | kBruteSliced) : 0;   // clustered or not, as above
@@ -1038,7 +1059,8 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     int wteam = 1;
     if (kTeamable) {
         wteam = fp.walk_team;
-        if (wteam == 0) wteam = auto_walk_team(fp.nloc, resident * block);
+        // (a listed add: the list's length is known on the device only -- one lane per pixel unless teams are set)
+        if (wteam == 0) wteam = ACC == kAccListed ? 1 : auto_walk_team(fp.nloc, resident * block);
         if (wteam != 2 && wteam != 4 && wteam != 8) wteam = 1;
     }
 
@@ -1054,7 +1076,7 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
             // (131k pixels) is fastest with single lanes (2.23 vs 2.29 ms with pairs), a 1/16 tile with
             // teams of 4 (1.67 vs 1.88 with pairs, 2.28 single)
             const int64_t lanes = resident * block;
-            f.team = fp.nloc * 4 <= lanes ? 4 : 1;
+            f.team = (ACC != kAccListed && fp.nloc * 4 <= lanes) ? 4 : 1;   // (a listed add: as for wteam above)
         }
     }
     f.walk_team = wteam;
@@ -1183,9 +1205,10 @@ __global__ void __launch_bounds__(256) debug_trace_kernel(DevScene S, const floa
 
 }  // namespace
 
-// rt_accum.hip compiles this file again with RT_ACCUM_TU defined: that translation unit holds the ACC
+// rt_accum.hip compiles this file again with RT_ACCUM_TU defined (1): that translation unit holds the ACC
 // instantiations of the kernels (through launch_accum) and none of the other entry points, so the code
 // object of this one -- every one-shot kernel -- is built from exactly what it was built from without them
+// (rt_adaptive.hip, RT_ACCUM_TU 2, does the same for the listed instantiations: launch_accum_listed, below)
 #ifndef RT_ACCUM_TU
 // FrameParams::slices as the last launch's kernel got it (rt_debug_last_slices: which kernel a test launched)
 static std::atomic<int> g_last_slices{0};
@@ -1242,7 +1265,7 @@ hipError_t launch_debug_trace(const DevScene& sc, int traversal, const float* ra
 
 #endif  // !RT_ACCUM_TU
 
-template <bool COUNT, bool STEP, bool ACC>
+template <bool COUNT, bool STEP, int ACC>
 hipError_t launch_resume(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
                          unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, bool smem, bool ovf) {
     if (smem)
@@ -1265,7 +1288,7 @@ static bool stage_in_lds(const DevScene& sc) {
     return sc.ntri > 0 && sc.nbrute == 0 && scene_bytes <= kLdsSceneMax && sc.stack_lds >= sc.depth;
 }
 
-template <bool COUNT, bool ACC = false>
+template <bool COUNT, int ACC = 0>
 hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
                        unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
     const bool ovf = sc.nbrute == 0 && sc.stack_lds < sc.depth;
@@ -1532,7 +1555,7 @@ hipError_t launch_render_pass(const DevScene& sc, const FrameParams& fp, int tra
 
 #endif  // !RT_ACCUM_TU
 
-#ifdef RT_ACCUM_TU
+#if defined(RT_ACCUM_TU) && RT_ACCUM_TU == 1
 // One add of a progressive accumulation: the ACC instantiation of the one-pass kernel launch_render_pass picks
 hipError_t launch_accum(const DevScene& sc, const FrameParams& f0, float4* state, int base, int traversal, int block,
                         float* d_out, unsigned int* d_work, hipStream_t stream) {
@@ -1541,12 +1564,212 @@ hipError_t launch_accum(const DevScene& sc, const FrameParams& f0, float4* state
     fp.pilot_state = state;
     fp.pilot = base;
     if (traversal == TRAV_REF)
-        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, true>(sc, fp, block, d_out, nullptr,
-                                                                                          d_work, stream);
-    return launch_fast<false, true>(sc, fp, block, d_out, nullptr, d_work, stream);
+        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, kAccAdd>(sc, fp, block, d_out, nullptr,
+                                                                                             d_work, stream);
+    return launch_fast<false, kAccAdd>(sc, fp, block, d_out, nullptr, d_work, stream);
 }
 
-#endif  // RT_ACCUM_TU
+#endif  // RT_ACCUM_TU == 1
+
+// rt_adaptive.hip compiles this file a third time (RT_ACCUM_TU 2): the kAccListed instantiations and the
+// selection's kernels, in a module of their own for the reason above -- the adds' code object stays what it was
+#if defined(RT_ACCUM_TU) && RT_ACCUM_TU == 2
+// A listed add (rt_accum_add_selected): f0.spp more samples of each of the *count pixels of list, every pixel
+// from the count its state holds.  One pass, one lane per pixel unless teams are set; no sample slices.
+hipError_t launch_accum_listed(const DevScene& sc, const FrameParams& f0, float4* state, const uint32_t* list,
+                               const uint32_t* count, int traversal, int block, float* d_out, unsigned int* d_work,
+                               hipStream_t stream) {
+    if (!state || !list || !count || f0.spp < 1 || f0.pass != 0 || f0.pilot != 0) return hipErrorInvalidValue;
+    FrameParams fp = f0;
+    fp.pilot_state = state;
+    fp.pilot_order = list;
+    fp.pilot_cost = const_cast<uint32_t*>(count);   // (read only: rt_internal.h)
+    fp.slices = 0;
+    fp.slice_state = nullptr;
+    fp.slice_ready = nullptr;
+    if (traversal == TRAV_REF)
+        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, kAccListed>(
+            sc, fp, block, d_out, nullptr, d_work, stream);
+    return launch_fast<false, kAccListed>(sc, fp, block, d_out, nullptr, d_work, stream);
+}
+
+// ---- adaptive sampling (rt_accum_mark / rt_accum_select*): which pixels a listed add refines ----
+namespace {
+constexpr int kSelBlock = 256;
+
+// tile pixel p is a pixel of the frame (not padding of a partial last row)
+__device__ __forceinline__ bool tile_pixel_real(int64_t p, int W, int row0, int row_step, int64_t npix) {
+    const int64_t krow = p / W;
+    return ((int64_t)row0 + krow * row_step) * W + (p - krow * W) < npix;
+}
+
+// clamp(acc / s), the operations of accum_resolve_kernel
+__device__ __forceinline__ rtm_f3 accum_colour(float4 a, int s) {
+    const rtm_f3 o = rtm_div(rtm_v3(a.x, a.y, a.z), (float)s);
+    return rtm_v3(rtm_fmax(rtm_fmin(o.x, 1.0f), 0.0f), rtm_fmax(rtm_fmin(o.y, 1.0f), 0.0f),
+                  rtm_fmax(rtm_fmin(o.z, 1.0f), 0.0f));
+}
+
+// rt_accum_mark: (acc.xyz, s) of every tile pixel
+__global__ void accum_mark_kernel(const float4* __restrict__ state, float4* __restrict__ mark, int64_t n) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const float4 a = state[2 * p];
+    mark[p] = make_float4(a.x, a.y, a.z, state[2 * p + 1].w);
+}
+
+// rt_accum_select: flag[p] = the pixel got samples since the mark and its error (rt_api.h) is above the threshold
+__global__ void select_error_kernel(const float4* __restrict__ state, const float4* __restrict__ mark,
+                                    uint8_t* __restrict__ flag, int64_t n, int W, int row0, int row_step, int64_t npix,
+                                    float threshold) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool sel = false;
+    if (tile_pixel_real(p, W, row0, row_step, npix)) {
+        const float4 a = state[2 * p], m = mark[p];
+        const int s1 = __float_as_int(state[2 * p + 1].w), s0 = __float_as_int(m.w);
+        const rtm_f3 c1 = accum_colour(a, s1), c0 = accum_colour(m, s0);
+        const float d = (rtm_fabs(c1.x - c0.x) + rtm_fabs(c1.y - c0.y)) + rtm_fabs(c1.z - c0.z);
+        const float e = d / dev_sqrt(((c1.x + c1.y) + c1.z) + 0.01f);
+        sel = s1 > s0 && e > threshold;   // (a NaN error compares false)
+    }
+    flag[p] = sel ? 1 : 0;
+}
+
+// rt_accum_select_mask / rt_accum_select_all: flag[p] = src[p] != 0 (src NULL: every pixel), padding pixels 0
+__global__ void select_mask_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ flag, int64_t n, int W,
+                                   int row0, int row_step, int64_t npix) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    flag[p] = (tile_pixel_real(p, W, row0, row_step, npix) && (!src || src[p] != 0)) ? 1 : 0;
+}
+
+// The ordered compaction, three launches: each block of kSelBlock pixels counts its flags; one block turns the
+// counts into exclusive offsets and stores their total (the list's length); each block then writes its flagged
+// pixels at its offset, in pixel order (a ballot per wave, the waves' totals through LDS).  So list is ascending
+// and the same on every run.
+__global__ void __launch_bounds__(kSelBlock) select_count_kernel(const uint8_t* __restrict__ flag, int64_t n,
+                                                                 uint32_t* __restrict__ block_count) {
+    __shared__ unsigned wtot[kSelBlock / 64];
+    const int64_t p = (int64_t)blockIdx.x * kSelBlock + threadIdx.x;
+    const bool sel = p < n && flag[p] != 0;
+    const unsigned long long b = __ballot(sel);
+    if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = (unsigned)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (int w = 0; w < kSelBlock / 64; ++w) t += wtot[w];
+        block_count[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(kSelBlock) select_scan_kernel(uint32_t* __restrict__ block_count, int64_t nblocks,
+                                                                uint32_t* __restrict__ total) {
+    __shared__ unsigned tsum[kSelBlock];
+    const int64_t per = (nblocks + kSelBlock - 1) / kSelBlock;
+    const int64_t lo0 = (int64_t)threadIdx.x * per, lo = lo0 < nblocks ? lo0 : nblocks;
+    const int64_t hi = lo + per < nblocks ? lo + per : nblocks;
+    unsigned t = 0;
+    for (int64_t q = lo; q < hi; ++q) t += block_count[q];
+    tsum[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned run = 0;
+        for (int q = 0; q < kSelBlock; ++q) {
+            const unsigned v = tsum[q];
+            tsum[q] = run;
+            run += v;
+        }
+        *total = run;
+    }
+    __syncthreads();
+    unsigned run = tsum[threadIdx.x];
+    for (int64_t q = lo; q < hi; ++q) {
+        const unsigned v = block_count[q];
+        block_count[q] = run;
+        run += v;
+    }
+}
+
+__global__ void __launch_bounds__(kSelBlock) select_compact_kernel(const uint8_t* __restrict__ flag, int64_t n,
+                                                                   const uint32_t* __restrict__ block_offset,
+                                                                   uint32_t* __restrict__ list) {
+    __shared__ unsigned wtot[kSelBlock / 64];
+    const int64_t p = (int64_t)blockIdx.x * kSelBlock + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool sel = p < n && flag[p] != 0;
+    const unsigned long long b = __ballot(sel);
+    if (lane == 0) wtot[wave] = (unsigned)__popcll(b);
+    __syncthreads();
+    unsigned off = block_offset[blockIdx.x];
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    // off + rank < the total of all flags <= n: within list's n entries
+    if (sel) list[off + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = (uint32_t)p;
+}
+
+// every tile pixel in order (a full add of an accumulation whose counts differ runs the listed kernel over it)
+__global__ void list_all_kernel(uint32_t* __restrict__ list, int64_t n, uint32_t* __restrict__ total) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) list[p] = (uint32_t)p;
+    if (p == 0) *total = (uint32_t)n;
+}
+
+// s of every tile pixel (rt_accum_sample_map)
+__global__ void sample_map_kernel(const float4* __restrict__ state, int32_t* __restrict__ out, int64_t n) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) out[p] = __float_as_int(state[2 * p + 1].w);
+}
+
+inline unsigned sel_grid(int64_t n) { return (unsigned)((n + kSelBlock - 1) / kSelBlock); }
+}  // namespace
+
+size_t select_scratch_words(int64_t n) { return (size_t)sel_grid(n) + 1; }
+
+hipError_t launch_accum_mark(const float4* state, float4* mark, int64_t n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_mark_kernel, dim3(sel_grid(n)), dim3(kSelBlock), 0, stream, state, mark, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_error(const float4* state, const float4* mark, uint8_t* flag, const FrameParams& fp,
+                               float threshold, hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_error_kernel, dim3(sel_grid(fp.nloc)), dim3(kSelBlock), 0, stream, state, mark, flag,
+                       fp.nloc, fp.width, fp.row0, fp.row_step, fp.npix, threshold);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_mask(const uint8_t* src, uint8_t* flag, const FrameParams& fp, hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_mask_kernel, dim3(sel_grid(fp.nloc)), dim3(kSelBlock), 0, stream, src, flag, fp.nloc,
+                       fp.width, fp.row0, fp.row_step, fp.npix);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_compact(const uint8_t* flag, int64_t n, uint32_t* scratch, uint32_t* list, uint32_t* count,
+                                 hipStream_t stream) {
+    if (n <= 0) return hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
+    const unsigned nb = sel_grid(n);
+    hipLaunchKernelGGL(select_count_kernel, dim3(nb), dim3(kSelBlock), 0, stream, flag, n, scratch);
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelBlock), 0, stream, scratch, (int64_t)nb, count);
+    hipLaunchKernelGGL(select_compact_kernel, dim3(nb), dim3(kSelBlock), 0, stream, flag, n,
+                       (const uint32_t*)scratch, list);
+    return hipGetLastError();
+}
+
+hipError_t launch_list_all(uint32_t* list, int64_t n, uint32_t* count, hipStream_t stream) {
+    if (n <= 0) return hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
+    hipLaunchKernelGGL(list_all_kernel, dim3(sel_grid(n)), dim3(kSelBlock), 0, stream, list, n, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_map(const float4* state, int32_t* out, int64_t n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sample_map_kernel, dim3(sel_grid(n)), dim3(kSelBlock), 0, stream, state, out, n);
+    return hipGetLastError();
+}
+
+#endif  // RT_ACCUM_TU == 2
 
 #ifndef RT_ACCUM_TU
 // rt_accum_read: the frame of an accumulation state, clamp(acc / s) as store_pixel writes it

@@ -156,6 +156,58 @@ int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], co
                           int64_t npix, int max_bounce, int row0, int row_step);
 int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream);
 
+/* Adaptive sampling: add samples only to the pixels that still need them.  The contract stays exact: a pixel
+ * that has received n samples holds the value of the one-shot frame at n spp, bit for bit, whatever the other
+ * pixels received (the state carries each pixel's own count, and a pixel's samples run in order over its own
+ * RNG chain).
+ *   rt_accum_mark        snapshot (sum, count) of every pixel: 16 bytes per pixel, in a buffer of its own per
+ *                        slot that is allocated on first use.
+ *   rt_accum_select      on the device, per pixel: c1 = clamp(sum / count) as rt_accum_read gives it, c0 the
+ *                        same from the mark, and in fp32, evaluated in this order without contraction,
+ *                            d = (|c1.x - c0.x| + |c1.y - c0.y|) + |c1.z - c0.z|
+ *                            n = sqrt(((c1.x + c1.y) + c1.z) + 0.01f)        (correctly rounded)
+ *                            e = d / n                                       (correctly rounded)
+ *                        The pixel is selected iff it received samples since the mark and e > threshold (a
+ *                        NaN error does not select).  The selected pixels are kept as a list in ascending
+ *                        pixel order, built by a scan -- the same list on every run; *n_selected (may be
+ *                        NULL) receives its length.
+ *   rt_accum_select_mask the same list from the caller's mask[npix] (non-zero = selected): a region of
+ *                        interest, or a policy of the caller's own.  rt_accum_select_all selects every pixel.
+ *   rt_accum_selection   the current selection as a 0/1 mask_out[npix].
+ *   rt_accum_sample_map  out[npix] = samples done, pixel by pixel.
+ *   rt_accum_add_selected  spp >= 1 more samples of every selected pixel, each continuing from its own count,
+ *                        blocking; out_rgb[3*npix] (may be NULL) receives the whole frame, clamp(sum / count) at
+ *                        each pixel's own count.  An empty selection adds nothing (RT_OK, the frame as it is).
+ *                        The selection stays: it may be added to again.
+ * After a selected add the counts differ: rt_accum_samples returns the largest a pixel can hold (the full adds
+ * plus every selected add -- the largest count itself when the selections were nested, as rt_accum_select's
+ * are), RT_ACCUM_MAX_SAMPLES is checked against it, and rt_accum_add still adds spp samples to every pixel,
+ * each from its own count.
+ * RT_ERR_STATE: rt_accum_select without a mark; rt_accum_add_selected and rt_accum_selection without a
+ * selection; rt_accum_add_selected before the first rt_accum_add (every pixel needs a sample: its cached
+ * camera hit); mark, select and sample map before any sample; any of them after an invalidation.  RT_ERR_ARG:
+ * spp < 1, or an add past RT_ACCUM_MAX_SAMPLES; nothing is added.  Mark and selection are dropped by begin, by
+ * end and by whatever invalidates the accumulation.
+ * Scheduling: a selected add is one pass over the list -- no pilot, no trails, no sample slices ("pilot",
+ * "spec" and "slices" do not apply) -- with one lane per pixel unless "team" / "walk_team" are set, which are
+ * honoured with the same bits. */
+int rt_accum_mark(rt_ctx* ctx);
+int rt_accum_select(rt_ctx* ctx, float threshold, int64_t* n_selected);
+int rt_accum_select_mask(rt_ctx* ctx, const uint8_t* mask);
+int rt_accum_select_all(rt_ctx* ctx);
+int rt_accum_selection(rt_ctx* ctx, uint8_t* mask_out);
+int rt_accum_sample_map(rt_ctx* ctx, int32_t* out);
+int rt_accum_add_selected(rt_ctx* ctx, int spp, float* out_rgb);
+/* Tile forms: one slot, the HIP stream `stream`, enqueue only, as rt_accum_add_device is -- none of them waits,
+ * the list's length stays in device memory, and a select followed by rt_accum_add_selected_device on the same
+ * stream needs no host wait in between.  d_mask is DEVICE memory, one byte per tile pixel, packed as the
+ * tile's rows are (rt_tile_rows x width); d_out as for rt_accum_add_device, the whole tile. */
+int rt_accum_mark_device(rt_ctx* ctx, int device_index, void* stream);
+int rt_accum_select_device(rt_ctx* ctx, int device_index, float threshold, void* stream);
+int rt_accum_select_mask_device(rt_ctx* ctx, int device_index, const uint8_t* d_mask, void* stream);
+int rt_accum_select_all_device(rt_ctx* ctx, int device_index, void* stream);
+int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),
