@@ -242,6 +242,7 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.ncslot = (int32_t)(ctx->hs.brute_cbox.size() / 8);
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
     s.cluster_auto = ctx->brute_cluster < 0 ? 1 : 0;
+    s.nsingle = ctx->hs.nsingle;
     s.stack_lds = std::min<int32_t>(s.depth > 0 ? s.depth : 1,
                                     ctx->stack_lds > 0 ? ctx->stack_lds : wide ? rt::kStackLdsWide : rt::kStackLds);
     s.stack_ovf = (int2*)d.stack_ovf.p;

@@ -449,6 +449,10 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// a width of the lock-step walk's pieces, as a type (trace_brute_compact)
+template <int N> struct IntC { static constexpr int value = N; };
+static_assert(kBoxGroup == 1 || kBoxGroup == 2 || kBoxGroup == 4 || kBoxGroup == 8, "the lock-step tail is cut into powers of two");
+
 // Teams (ts = 2, 4 or 8 lanes per pixel, when a tile has fewer pixels than the GPU has lanes):
 // the ts lanes of a team carry the same path (identical arithmetic), split the box tests between
 // them (lane `sub` of the team tests records sub, sub + ts, ...; records read from the LDS copy
@@ -532,41 +536,58 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             bk = __uint_as_float((unsigned)(bestk[tl] >> 32));
         }
     };
-    // kBoxGroup distinct leaf boxes per scalar wait: the group is loaded together (2 float4 per box:
-    // the box and its one or two records; padded with boxes that list record 0), all its slab tests run back
-    // to back, then the passes are queued (culling uses the best hit as of the group's start:
-    // conservative).  Slots [gb, ge) of cb; nreal: the real slots of the array (instrumented build)
-    auto lockstep = [&](const ConstF4 cb, int gb, int ge, int nreal) __attribute__((always_inline)) {
-        for (int g0 = gb; g0 < ge; g0 += kBoxGroup) {
-            float4 bx[2 * kBoxGroup];
+    // W distinct leaf boxes per scalar wait: slots [g0, g0 + W) of cb are loaded together (2 float4 per box:
+    // the box and its one or two records), all their slab tests run back to back, then the passes are queued
+    // (culling uses the best hit as of the group's start: conservative).  nreal: the real slots of the array
+    // (instrumented build)
+    auto group = [&](auto wc, const ConstF4 cb, int g0, int nreal) __attribute__((always_inline)) {
+        constexpr int W = decltype(wc)::value;
+        float4 bx[2 * W];
 #pragma unroll
-            for (int j = 0; j < 2 * kBoxGroup; ++j) bx[j] = sgpr4(cb[2 * g0 + j]);
-            const float cull = bk * CULL_MARGIN;
-            bool pass[kBoxGroup];
+        for (int j = 0; j < 2 * W; ++j) bx[j] = sgpr4(cb[2 * g0 + j]);
+        const float cull = bk * CULL_MARGIN;
+        bool pass[W];
 #pragma unroll
-            for (int j = 0; j < kBoxGroup; ++j) {
-                float tn, tx;
-                slab(bx[2 * j].x, bx[2 * j].y, bx[2 * j].z, bx[2 * j].w, bx[2 * j + 1].x, bx[2 * j + 1].y, o, ix, iy,
-                     iz, tn, tx);
-                pass[j] = box_hit(tn, tx, cull);
-            }
-#pragma unroll
-            for (int j = 0; j < kBoxGroup; ++j) {
-                // padding boxes (a point at 1e30 listing record 0 alone, scene_pack.cpp pad_box) pass only for
-                // rays with a NaN component (slab() and box_hit() drop NaN) or from about 1e30 (1, 1, 1); the
-                // product build queues them without a check (r06: the 1/8 tile 2.19 -> 2.16 ms, the frame
-                // unchanged): such a pass tests record 0 once more for its owner, which cannot change the
-                // owner's minimum (k, rank) key.  The instrumented build skips them so the counters stay exact
-                if (COUNT && g0 + j >= nreal) break;
-                const int qa = __float_as_int(bx[2 * j + 1].z), qb = __float_as_int(bx[2 * j + 1].w);
-                if (COUNT) {   // counted per record (one leaf box test each, as in the tree walk)
-                    c.boxes++;
-                    count_wave(c.wave_trav); c.nodes++;
-                    if (qb >= 0) { count_wave(c.wave_trav); c.nodes++; }
-                }
-                enqueue(pass[j], (unsigned)qa, qb);
-            }
+        for (int j = 0; j < W; ++j) {
+            float tn, tx;
+            slab(bx[2 * j].x, bx[2 * j].y, bx[2 * j].z, bx[2 * j].w, bx[2 * j + 1].x, bx[2 * j + 1].y, o, ix, iy, iz,
+                 tn, tx);
+            pass[j] = box_hit(tn, tx, cull);
         }
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            // padding boxes (a point at 1e30 listing record 0 alone, scene_pack.cpp pad_box) pass only for
+            // rays with a NaN component (slab() and box_hit() drop NaN) or from about 1e30 (1, 1, 1); the
+            // product build queues them without a check (r06: the 1/8 tile 2.19 -> 2.16 ms, the frame
+            // unchanged): such a pass tests record 0 once more for its owner, which cannot change the
+            // owner's minimum (k, rank) key.  The instrumented build skips them so the counters stay exact
+            if (COUNT && g0 + j >= nreal) break;
+            const int qa = __float_as_int(bx[2 * j + 1].z), qb = __float_as_int(bx[2 * j + 1].w);
+            if (COUNT) {   // counted per record (one leaf box test each, as in the tree walk)
+                c.boxes++;
+                count_wave(c.wave_trav); c.nodes++;
+                if (qb >= 0) { count_wave(c.wave_trav); c.nodes++; }
+            }
+            enqueue(pass[j], (unsigned)qa, qb);
+        }
+    };
+    // slots [gb, ge) of cb in whole groups of kBoxGroup, the padding slots of the last one included (the
+    // unclustered loop over brute_box: its tiles run half-empty waves that wait on round trips, not on VALU
+    // issue, and the exact walk below measured slower there)
+    auto lockstep_padded = [&](const ConstF4 cb, int gb, int ge) __attribute__((always_inline)) {
+        for (int g0 = gb; g0 < ge; g0 += kBoxGroup) group(IntC<kBoxGroup>{}, cb, g0, ge);
+    };
+    // slots [gb, ge) of cb and no other: whole groups of kBoxGroup, then the remaining 1 .. kBoxGroup - 1 slots
+    // in pieces of decreasing width, each loaded and tested alone with a scalar wait of its own.  The arrays stay
+    // padded to whole groups in memory, but no padding slot is tested here (the clustered loop: C2's 6 single
+    // slots are a group and a pair, not two groups with two padding tests per ray)
+    auto lockstep = [&](const ConstF4 cb, int gb, int ge) __attribute__((always_inline)) {
+        int g0 = gb;
+        for (; g0 + kBoxGroup <= ge; g0 += kBoxGroup) group(IntC<kBoxGroup>{}, cb, g0, ge);
+        const int rem = ge - g0;
+        if constexpr (kBoxGroup > 4) if (rem & 4) group(IntC<4>{}, cb, g0 + (rem & ~7), ge);
+        if constexpr (kBoxGroup > 2) if (rem & 2) group(IntC<2>{}, cb, g0 + (rem & ~3), ge);
+        if constexpr (kBoxGroup > 1) if (rem & 1) group(IntC<1>{}, cb, g0 + (rem & ~1), ge);
     };
     // (CLU kernels are launched for clustered scenes only, launch_t: they carry no loop over brute_box)
     if (CLU) {
@@ -575,7 +596,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         const unsigned* besthi = reinterpret_cast<const unsigned*>(bestk) + 1;              // distance bits of bestk[i] at [2 i]
         inv[lane] = ix; inv[64 + lane] = iy; inv[128 + lane] = iz;
         const ConstF4 cb = as_const(S.brute_cbox);
-        lockstep(cb, 0, S.nsingle4, S.nsingle4);
+        lockstep(cb, 0, S.nsingle);
         unsigned ihead = 0, itail = 0;   // wave-uniform item positions; itail is a multiple of kClusterSlots
         // one batch of n <= nact items: fewer than nact pairs are queued before it and it adds at most 2 n
         auto run_items = [&](int n) __attribute__((always_inline)) {
@@ -622,7 +643,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             const int np = __popcll(m);
             const int first = __float_as_int(u1.z);
             if (np > lock) {
-                lockstep(cb, first, first + kClusterSlots, S.ncslot);
+                lockstep(cb, first, first + __float_as_int(u1.w));   // the cluster's real boxes
                 continue;
             }
             // np <= lock < nact owners join fewer than nact / kClusterSlots + 1 waiting ones: the list never
@@ -634,7 +655,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         }
         while (itail != ihead) run_items(min((int)(itail - ihead), nact));
     } else if (ts == 1) {
-        lockstep(as_const(S.brute_box), 0, S.nbox, S.nbox);
+        lockstep_padded(as_const(S.brute_box), 0, S.nbox);
     } else {
         // box g = gg * ts + sub of each round (LDS copy of brute_box at boxrec); its second record, when
         // there is one, differs between the lanes of the wave: queued by a second call

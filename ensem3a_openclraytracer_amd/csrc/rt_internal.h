@@ -81,6 +81,11 @@ struct DevScene {
     const float4* brute_crow;
     int32_t ncluster, ncslot, nsingle4;
     int32_t cluster_auto;   // option "brute_cluster" is -1: launch_t clusters only tiles of at least a pixel per resident lane
+    // the real single slots at the head of brute_cbox.  The clustered loop tests slots [0, nsingle) and, where a
+    // cluster runs lock-step, its `count` boxes in whole groups of kBoxGroup and then the last 1..3 alone: the
+    // padding slots stay in memory -- a group load never leaves the buffer, an item's slot index is a shift and
+    // a mask -- but only an item tests one
+    int32_t nsingle;
 };
 
 struct FrameParams {
