@@ -38,6 +38,7 @@ EXPORTED = (
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
+    "rt_debug_brute_refill", "rt_debug_last_refill",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
@@ -146,6 +147,8 @@ def lib():
                                                _c_p, _i64, _c_p, _i64, _c_p]),
             "rt_debug_brute_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _c_p]),
             "rt_debug_last_slices": (_i32, []),
+            "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
+            "rt_debug_last_refill": (_i32, [_c_p]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
@@ -289,7 +292,7 @@ class Context:
 
     COUNT_KEYS = ("node_fetches", "tri_tests", "rays", "env_lookups", "stack_drops", "wave_trav_iters",
                   "wave_render_iters", "cycles_shade", "cycles_trav", "box_tests", "ev_diffuse", "ev_glossy",
-                  "ev_glass", "sun_terms", "samples")
+                  "ev_glass", "sun_terms", "samples", "refill_events")
 
     def count_work_detail(self, cam, env, npix, spp, max_bounce, row0=0, row_step=1):
         """rt_count_work_detail: every work counter of the instrumented render of the tile."""
@@ -579,6 +582,26 @@ def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: 
 def last_slices() -> int:
     """rt_debug_last_slices: the slice word the last render launch's kernel got (0: unsliced)."""
     return int(lib().rt_debug_last_slices())
+
+
+def brute_refill(nloc: int, lanes: int, option: int = -1) -> int:
+    """rt_debug_brute_refill (include/rt_debug.h): the refill threshold R of the one-lane brute-force kernels
+    (0: every free lane is refilled at once), from the host's rule alone."""
+    out = np.zeros(1, np.int32)
+    st = lib().rt_debug_brute_refill(int(nloc), int(lanes), int(option), out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_debug_brute_refill: bad arguments")
+    return int(out[0])
+
+
+def last_refill():
+    """rt_debug_last_refill: ``(R, events, lanes)`` -- the threshold the last render launch's kernel got, and the
+    refill counters of the last instrumented launch."""
+    out = np.zeros(3, np.int64)
+    st = lib().rt_debug_last_refill(out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_debug_last_refill: bad arguments")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def tile_rows(npix: int, width: int, row0: int, row_step: int) -> int:

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <map>
@@ -114,6 +115,7 @@ struct rt_ctx {
     int wdq = 1;          // 4-wide walk: origin-folded dequantisation where the builder's gap covers the frame (option "wdq")
     int handout = -1;     // pixel hand-out: 0 = interleaved chunks, 1 = a contiguous block per XCD group, -1 = auto
     int slices = -1;      // one-pass tree-walk launches: sample slices per pixel (FrameParams::slices; 0 off, -1 auto)
+    int brute_refill = -1;   // one-lane brute-force kernels: free lanes a wave refills together (FrameParams::refill; -1 auto, 0 or 1 off, R)
     bool accum_host = false;   // the open accumulation is rt_accum_begin's: every slot holds its rows of one frame
     // host wall times of the last calls (rt_debug_timings), ms: rt_set_scene's validation + packing and its
     // uploads (+ the per-triangle frame kernel), rt_set_env (upload + texel-sum kernel), rt_render's
@@ -287,6 +289,7 @@ int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, i
     fp->spec_log = nullptr;
     fp->spec_cap = 0;
     fp->slices = 0;
+    fp->refill = ctx->brute_refill;   // the option: launch_t makes R of it (rt_internal.h brute_refill_launch)
     fp->slice_state = nullptr;
     fp->slice_ready = nullptr;
     fp->pilot_cost = nullptr;
@@ -504,6 +507,12 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
     if (!std::strcmp(key, "slices")) {
         if (value < -1 || value > 16) return set_err(ctx, RT_ERR_ARG, "slices must be -1 (auto), 0 (off) or 1..16");
         ctx->slices = (int)value;
+        return RT_OK;
+    }
+    if (!std::strcmp(key, "brute_refill")) {
+        if (value < -1 || value > rt::kRefillMax)
+            return set_err(ctx, RT_ERR_ARG, "brute_refill must be -1 (auto), 0 or 1 (off) or 2..%d", rt::kRefillMax);
+        ctx->brute_refill = (int)value;
         return RT_OK;
     }
     if (!std::strcmp(key, "wdq")) {
@@ -1467,6 +1476,8 @@ int rt_rgb8(rt_ctx* ctx, const float* in, uint8_t* out, int64_t n, int gamma) {
 }
 
 namespace {
+// the refill counters of the last instrumented launch (rt_debug_last_refill)
+std::atomic<long long> g_refill_events{0}, g_refill_lanes{0};
 int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce, int row0,
               int row_step, uint64_t* counts, int n) {
     rt::FrameParams fp;
@@ -1479,7 +1490,7 @@ int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t bytes = (size_t)fp.nloc * 3 * sizeof(float);
     HIP_OR_RET(ctx, ensure(d.out, bytes > 0 ? bytes : 16));
-    unsigned long long h[16] = {0};
+    unsigned long long h[18] = {0};   // the kernels' counters (rt_device.h NCOUNTS), then render_kernel's refill events [15] and lanes refilled [16]
     HIP_OR_RET(ctx, ensure(d.counts, sizeof h));
     HIP_OR_RET(ctx, hipMemsetAsync(d.counts.p, 0, sizeof h, d.stream));
     HIP_OR_RET(ctx, order_after_last(d, d.stream));
@@ -1492,6 +1503,8 @@ int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix
     HIP_OR_RET(ctx, hipMemcpyAsync(h, d.counts.p, sizeof h, hipMemcpyDeviceToHost, d.stream));
     HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
     for (int q = 0; q < n; ++q) counts[q] = h[q];
+    g_refill_lanes.store((long long)h[16], std::memory_order_relaxed);   // (rt_debug_last_refill; h[15] = the events)
+    g_refill_events.store((long long)h[15], std::memory_order_relaxed);
     return RT_OK;
 }
 }  // namespace
@@ -1627,6 +1640,20 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 }
 
 int rt_debug_last_slices(void) { return rt::last_launch_slices(); }
+
+int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out) {
+    if (!out || nloc < 0 || lanes < 0 || option < -1 || option > rt::kRefillMax) return RT_ERR_ARG;
+    *out = rt::brute_refill_launch(option, nloc, lanes);
+    return RT_OK;
+}
+
+int rt_debug_last_refill(int64_t out[3]) {
+    if (!out) return RT_ERR_ARG;
+    out[0] = rt::last_launch_refill();
+    out[1] = g_refill_events.load(std::memory_order_relaxed);
+    out[2] = g_refill_lanes.load(std::memory_order_relaxed);
+    return RT_OK;
+}
 
 int rt_debug_timings(rt_ctx* ctx, double out[4]) {
     if (!ctx || !out) return set_err(ctx, RT_ERR_ARG, "bad arguments");

@@ -991,7 +991,7 @@ typedef unsigned long long __attribute__((address_space(1))) gu64;
 // Correctness does not depend on the placement: every pixel is taken exactly once whatever XCD a
 // block runs on.
 struct PixelQueue {
-    unsigned dry = 0;   // bit g: group g's counter is exhausted
+    unsigned dry = 0;   // bit g: group g's counter is exhausted (from bit 8: render_kernel's refill threshold, take_pixel NEAR)
     // FrameParams::handout = 1: group g owns the contiguous pixels [g per, (g + 1) per) of the tile instead
     // of every kGroups-th chunk, so one XCD's rays in flight come from one region of the image (the tree's
     // lines they need are fewer: the L2 of an XCD holds more of them).  0: interleaved chunks.
@@ -1020,6 +1020,14 @@ __device__ __forceinline__ unsigned group_pixels(unsigned g, unsigned nloc, unsi
 // slices > 1 (FrameParams::slices): a group hands out `slices` passes over its pixels, slice-major --
 // the job after its pixels' slice k is their slice k + 1 -- and the return value is the job
 // k * nloc + pixel (>= slices * nloc: none left).
+// NEAR (the one-lane brute-force kernels, FrameParams::refill): Q.dry carries the caller's refill threshold R
+// above the groups' bits (render_kernel), and it is cleared once a group's sequence comes within a wave's worth
+// of jobs of its end, or past it -- from then on the caller refills every free lane at once, so the end of a
+// tile idles no lane behind the threshold.  The other callers' code is what it was.
+constexpr int kQueueRefillShift = 8;
+constexpr unsigned kQueueGroupBits = (1u << kQueueRefillShift) - 1u;
+static_assert(kGroups <= kQueueRefillShift, "PixelQueue::dry: the groups' bits lie below the refill threshold");
+template <bool NEAR = false>
 __device__ __forceinline__ unsigned take_pixel(PixelQueue& Q, unsigned long long need, int lane0,
                                                unsigned* __restrict__ counters, unsigned nloc, int lane,
                                                unsigned slices = 1) {
@@ -1039,6 +1047,7 @@ __device__ __forceinline__ unsigned take_pixel(PixelQueue& Q, unsigned long long
         const unsigned px = group_pixels(g, nloc, Q.per);
         const unsigned have = px * slices;
         const unsigned nok = j0 < have ? min(have - j0, k) : 0u;
+        if (NEAR && j0 + k + 64u >= have) Q.dry &= kQueueGroupBits;
         if (mine && rank >= base && rank < base + nok) {
             const unsigned jj = j0 + (rank - base);
             q = slices == 1 ? group_pixel(g, jj, Q.per) : (jj / px) * nloc + group_pixel(g, jj % px, Q.per);
@@ -1055,6 +1064,7 @@ __device__ __forceinline__ unsigned take_pixel(PixelQueue& Q, unsigned long long
 // slice-major.  Returns the pixel (nloc: none left) and in job_slice its slice, kWholeJob for a whole
 // pixel -- no job number for the caller to divide.
 constexpr unsigned kWholeJob = 0xffffffffu;
+template <bool NEAR = false>
 __device__ __forceinline__ unsigned take_job(PixelQueue& Q, unsigned long long need, int lane0,
                                              unsigned* __restrict__ counters, unsigned nloc, int lane,
                                              unsigned slices, unsigned tail, unsigned& job_slice) {
@@ -1076,6 +1086,7 @@ __device__ __forceinline__ unsigned take_job(PixelQueue& Q, unsigned long long n
         const unsigned ps = px - pw;                                                  // sliced pixels
         const unsigned have = pw + ps * slices;
         const unsigned nok = j0 < have ? min(have - j0, k) : 0u;
+        if (NEAR && j0 + k + 64u >= have) Q.dry &= kQueueGroupBits;
         if (mine && rank >= base && rank < base + nok) {
             const unsigned jj = j0 + (rank - base);
             if (jj < pw) {

@@ -134,6 +134,12 @@ struct FrameParams {
     // trail's log of (RNG offset, sample colour) records, spec_cap records per trail; one log per resident
     // lane (a team's trails log the pixel it holds; the logs are reused from record 0 for its next pixel)
     int32_t spec;
+    // One-lane brute-force kernels (render_kernel; option "brute_refill", rule below: brute_refill_launch): a
+    // wave hands out jobs only once this many of its lanes are free -- or none of its lanes traces, or its
+    // hand-out is near its end -- so the hand-out's code, which the whole wave steps through, runs for
+    // several lanes at a time.  0 or 1: every lane is refilled at once.  (It stands where the structure had
+    // padding: no other field moves, and no kernel's arguments do.)
+    int32_t refill;
     float4* spec_log;
     int32_t spec_cap;
     // Sample slices (option "slices", one-pass launches of the tree walk): each pixel's samples are
@@ -238,7 +244,24 @@ size_t spec_log_bytes(const FrameParams& fp, int cus);
 hipError_t launch_spec(const DevScene& sc, const FrameParams& fp, int block, float* d_out, unsigned int* d_work,
                        hipStream_t stream);
 bool spec_walk(const DevScene& sc, const FrameParams& fp);
+// The host's rule for FrameParams::refill (option "brute_refill": -1 auto, 0 or 1 off, R >= 2 set).  launch_t
+// applies it where it knows its kernel's resident lanes; rt_debug_brute_refill evaluates it for
+// tests/test_brute_refill_rule.py (no frame depends on it).  Auto: R = kRefillBrute on tiles of at least 1.5
+// pixels per resident lane (the boundary of the sample slices, rt_slices.h: below it the waves run half empty
+// and a waiting lane is a larger share of the work), off elsewhere -- such a launch runs the kernels without the
+// threshold's code (launch_t).  C2 (r12; ms per frame, the parent 6.45): R = 1 / 4 / 6 / 8 / 16
+// 6.48-6.52 / 6.28-6.30 / 6.27-6.29 / 6.28-6.31 / 6.54; rows 0::2 (1.6 pixels per lane) 3.74 -> 3.64
+constexpr int kRefillBrute = 4;
+constexpr int kRefillMax = 64;
+inline int brute_refill_launch(int option, int64_t nloc, int64_t lanes) {
+    if (option >= 0) return option >= 2 ? (int)std::min<int64_t>(option, kRefillMax) : 0;
+    return brute_auto_slices(nloc, lanes) ? kRefillBrute : 0;
+}
 // test hooks
+// FrameParams::refill as the kernel of the last launch_t got it (0: every lane refilled at once), and the refill
+// counters of the last instrumented launch (count_all)
+void note_launch_refill(int v);
+int last_launch_refill();
 // FrameParams::slices as the kernel of the last launch_t got it (0: an unsliced launch)
 void note_launch_slices(int v);
 int last_launch_slices();

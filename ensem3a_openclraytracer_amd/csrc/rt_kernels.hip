@@ -59,6 +59,10 @@ constexpr int kAccListed = 2;
 // that hand out sample slices (FrameParams::slices; one lane per pixel: 1 and 3 only) -- instantiations of
 // their own again, so that an unsliced launch runs the code it ran without them
 constexpr int kBruteSliced = 4;
+// ... and + kBruteRefill for the launches with a refill threshold (FrameParams::refill > 1; one lane per pixel
+// again), so that a launch without one -- the small tiles, where the threshold measured slower -- runs the code
+// it ran before.  The instrumented and logging kernels (COUNT, LOG) carry the threshold's code without the flag
+constexpr int kBruteRefill = 8;
 template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, int ACC = 0>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
@@ -73,6 +77,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     constexpr int BRUTE = BRUTE_ & 3;
     constexpr bool SLICED = (BRUTE_ & kBruteSliced) != 0;
     static_assert(!SLICED || BRUTE == 1 || BRUTE == 3, "sample slices: the one-lane brute-force loops");
+    constexpr bool kRefill = (BRUTE == 1 || BRUTE == 3) && ((BRUTE_ & kBruteRefill) != 0 || COUNT || LOG);
+    static_assert(!(BRUTE_ & kBruteRefill) || BRUTE == 1 || BRUTE == 3, "refill threshold: the one-lane brute-force loops");
     extern __shared__ int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
@@ -142,6 +148,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     int phase = FETCH;
     PixelQueue pq;
     pq.per = (F.handout && F.pass != 2) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
+    // FrameParams::refill = R rides in the hand-out's word, which the loop keeps anyway (a scalar register of
+    // its own spills others that the shading reads)
+    if constexpr (kRefill) pq.dry = F.refill > 1 ? (unsigned)min(F.refill, 64) << kQueueRefillShift : 0u;
     int p = 0, i = 0;
     bool logme = false;
     uint32_t seed0 = 0, seed1 = 0;
@@ -164,6 +173,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     int cost = 0;   // pass 1: rays this pixel traced (pilot_cost)
     int sun0 = -2;  // the first bounce's shadow-ray hit (-1 = miss; -2 = not traced yet)
     unsigned long long t_prev = 0;   // COUNT: the wave clock at the previous loop head
+    // COUNT, lane 0 for its wave: loop iterations that ran the hand-out block (take_pixel / take_job and the job's
+    // start-up) and the lanes that asked for a job in them -- counts[15] and [16], after the counters of Cnt
+    [[maybe_unused]] unsigned long long refill_ev = 0, refill_lanes = 0;
     // pass 1 (FrameParams::pass): after the pilot samples, save the pixel's state for pass 2; the
     // pixel is written (and its cost set to 0) when all its samples are done
     auto save_pilot = [&]() __attribute__((always_inline)) {
@@ -205,12 +217,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         }
         // -- refill: ballot the lanes that need a pixel, one atomic per wave --
         // teams (BRUTE, F.team lanes per pixel): one bit per team, the team's lanes take the same pixel
-        const unsigned long long need = __ballot(phase == FETCH) & team_leaders;
+        unsigned long long need = __ballot(phase == FETCH) & team_leaders;
+        // the one-lane brute-force loops (FrameParams::refill = R > 1): the block below is stepped through by
+        // the whole wave for however few lanes ask, so the free lanes wait until R of them ask together.  They
+        // never wait (a) with R lanes free, (b) in a wave none of whose lanes holds a ray or a sample to shade --
+        // need is cleared only while such a lane exists, and every such lane ends its job after finitely many
+        // rounds, so a waiting lane is always served -- or (c) once the hand-out is near its end (take_pixel
+        // NEAR clears R).  A finished job is published where it ends (store_pixel, save_slice: below), never
+        // behind a waiting lane
+        if constexpr (kRefill) {
+            if (need && (unsigned)__popcll(need) < (pq.dry >> kQueueRefillShift)) {
+                const unsigned long long busy = __ballot(phase != FETCH && phase != DONE && phase != WAIT_SLICE);
+                if (busy) need = 0;
+            }
+        }
+        if (COUNT && need && lane == 0) {
+            refill_ev++;
+            refill_lanes += (unsigned)__popcll(need);
+        }
         if (need) {
             unsigned sl = kWholeJob;   // SLICED: the job's slice, or a whole pixel
             unsigned int q;
-            if constexpr (SLICED) q = take_job(pq, need, team_lane0, work_counter, nloc, lane, nsl, stail, sl);
-            else q = take_pixel(pq, need, team_lane0, work_counter, nloc, lane);
+            if constexpr (SLICED) q = take_job<kRefill>(pq, need, team_lane0, work_counter, nloc, lane, nsl, stail, sl);
+            else q = take_pixel<kRefill>(pq, need, team_lane0, work_counter, nloc, lane);
             if (SLICED && phase == FETCH && q < nloc && sl != kWholeJob && sl > 0) {
                 // continues a pixel once its slice sl - 1 is done (below): all it needs is in that slice's state
                 p = (int)q;
@@ -484,6 +513,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             unsigned long long x = v[q];
             for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
             if (lane == 0 && x) atomicAdd(&counts[q], x);
+        }
+        if (BRUTE && lane == 0) {   // the hand-out's counters: lane 0 keeps its wave's
+            atomicAdd(&counts[NCOUNTS], refill_ev);
+            atomicAdd(&counts[NCOUNTS + 1], refill_lanes);
         }
     }
 }
@@ -1053,6 +1086,9 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
         bslices = brute_slice_launch(fp.slices, fp.nloc, resident * block);
     constexpr int kBruteSl = BRUTE ? (kBruteClu | kBruteSliced) : 0;   // clustered or not, as above
     constexpr int kBruteSl1 = BRUTE ? (1 | kBruteSliced) : 0;
+    // the product kernels with a refill threshold are instantiations of their own (the instrumented and logging
+    // ones carry its code anyway)
+    constexpr int kBruteRf = (BRUTE && !RESUME && !COUNT && !LOG) ? kBruteRefill : 0;
     // team walk (render_resume_kernel TEAM): BVH2 item steps only; walk_team, 0 = auto (auto_walk_team;
     // pass 2 of a pilot launch: the size pilot_team_pick_kernel chose, launch_render)
     constexpr bool kTeamable = RESUME && STEP && !WIDE && !LOG;
@@ -1080,6 +1116,10 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
         }
     }
     f.walk_team = wteam;
+    // the refill threshold of the one-lane brute-force kernels (fp.refill: the option; f.refill: R, or 0), from
+    // the resident lanes of the kernel picked above (the sliced instantiations keep the same five waves)
+    f.refill = (BRUTE && !RESUME && f.team <= 1) ? brute_refill_launch(fp.refill, fp.nloc, resident * block) : 0;
+    note_launch_refill(f.refill);   // (rt_debug_last_refill)
     const int64_t need = (fp.nloc * f.team * wteam + block - 1) / block;
     int64_t grid = std::min(need, resident);
     // the team instantiations (TS = 2, 4, 8) and their own occupancy
@@ -1146,7 +1186,17 @@ hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float*
     else if (RESUME)
         hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>), dim3((unsigned)grid), dim3(block), lds, stream,
                            sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else if (BRUTE && bslices && clu)
+    else if (kBruteRf && f.refill > 1) {
+        // the instantiations with the refill threshold (same registers and LDS as their twins below: the grid stands)
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
+                               (const LaunchConst*)lc);
+        };
+        if (bslices && clu) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl | kBruteRf, ACC>);
+        else if (bslices) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1 | kBruteRf, ACC>);
+        else if (clu) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu | kBruteRf, ACC>);
+        else go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, (BRUTE ? 1 : 0) | kBruteRf, ACC>);
+    } else if (BRUTE && bslices && clu)
         hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl, ACC>), dim3((unsigned)grid),
                            dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
     else if (BRUTE && bslices)
@@ -1214,6 +1264,9 @@ __global__ void __launch_bounds__(256) debug_trace_kernel(DevScene S, const floa
 static std::atomic<int> g_last_slices{0};
 void note_launch_slices(int v) { g_last_slices.store(v, std::memory_order_relaxed); }
 int last_launch_slices() { return g_last_slices.load(std::memory_order_relaxed); }
+static std::atomic<int> g_last_refill{0};
+void note_launch_refill(int v) { g_last_refill.store(v, std::memory_order_relaxed); }
+int last_launch_refill() { return g_last_refill.load(std::memory_order_relaxed); }
 
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

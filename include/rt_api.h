@@ -224,7 +224,8 @@ int rt_count_work(rt_ctx* ctx, const float cam[10], const float env[5], int64_t 
  * leaf box), [10]/[11]/[12] shading events (naiveGI bounces,
  * Raytracing.cl:58-78) on materials of type 1 (diffuse) / 2 (glossy) /
  * 3 (glass), [13] sun terms evaluated (Raytracing.cl:115-137), [14] samples,
- * [15] 0.  Feeds the VALU roofline of bench.py. */
+ * [15] render-loop iterations per wave that handed out jobs (the brute-force
+ * loops; with [6], the refill events per iteration).  Feeds the VALU roofline of bench.py. */
 int rt_count_work_detail(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp,
                          int max_bounce, int row0, int row_step, uint64_t counts[16]);
 

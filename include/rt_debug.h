@@ -15,6 +15,8 @@
  *   "team"         brute force: lanes per pixel 1/2/4/8 (0 auto by tile size)
  *   "brute_cluster"  brute force, one lane per pixel: groups of leaf boxes behind one union test, the passing
  *                  rays' (ray, box) tests compacted (0 off, 1 every SAH subtree of 2..8 boxes, -1 auto by cost)
+ *   "brute_refill" brute force, one lane per pixel: a wave hands out jobs once this many lanes are free, 2..64
+ *                  (0 or 1 every free lane at once, -1 auto: 4 on tiles of >= 1.5 pixels per resident lane)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
  *   "spec"         pass 2 of a pilot launch: speculative trails per pixel 2/4/8 (0 off, -1 auto)
  *   "slices"       one-pass tree-walk launches: sample slices per pixel 2..16 (0 off, -1 auto)
@@ -115,6 +117,17 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 /* What the kernel of the process's last render launch got as its slice word: 0 for an unsliced launch, K for the
  * tree walk, K | share << 8 (as above) for a sliced brute-force launch. */
 int rt_debug_last_slices(void);
+
+/* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
+ * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
+ * lanes of the kernel resident.  *out = R, the free lanes a wave waits for before it hands out jobs, or 0 when
+ * every free lane is refilled at once. */
+int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out);
+
+/* out[0] = R (as above) as the kernel of the process's last render launch got it; out[1], out[2] = the refill
+ * counters of the last instrumented launch (rt_count_work*): the render-loop iterations, per wave, that ran the
+ * hand-out block, and the lanes that asked for a job in them (out[1] is counts[15] of rt_count_work_detail). */
+int rt_debug_last_refill(int64_t out[3]);
 
 #ifdef __cplusplus
 }

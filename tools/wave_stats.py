@@ -15,7 +15,7 @@ from ensem3a_openclraytracer_amd import workloads as W  # noqa: E402
 
 # rt_set_option defaults of the options a set may change (rt_api.hip)
 DEFAULTS = {"spec": -1, "slices": -1, "pilot": -1, "resume_min": -1, "handout": -1, "bvh_width": 0, "brute_max": 64,
-            "block": 128, "fixed_point": 1, "sun_cache": 1}
+            "block": 128, "fixed_point": 1, "sun_cache": 1, "brute_refill": -1, "brute_cluster": -1}
 names = (sys.argv[1] if len(sys.argv) > 1 else "C3").split(",")
 sets = [dict(kv.split("=") for kv in filter(None, spec.split(",")))
         for spec in (sys.argv[2] if len(sys.argv) > 2 else "").split(";")]
@@ -43,6 +43,11 @@ for name in names:
             # in batches of their own outside the counted rounds, so it can exceed 1 (1.07 on C2 with slices);
             # it is kept for comparison with the profiles of earlier rounds
             out["brute_ray_fill"] = round(c["node_fetches"] / max(1, 64 * c["wave_trav_iters"]), 4)
+            # the hand-out block (option "brute_refill"): the share of a wave's loop iterations that ran it, and
+            # the lanes that asked for a job each time (rt_debug_last_refill)
+            r, ev, ln = _native.last_refill()
+            out["refill"] = {"R": r, "events_per_render_iter": round(ev / max(1, c["wave_render_iters"]), 4),
+                             "lanes_per_event": round(ln / max(1, ev), 3)}
         print(json.dumps(out), flush=True)
         if len(sys.argv) > 3:   # committed evidence (profiles/rNN_wave_stats.jsonl)
             with open(sys.argv[3], "a") as f:
