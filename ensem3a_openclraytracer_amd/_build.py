@@ -5,6 +5,7 @@ Output: ``ensem3a_openclraytracer_amd/lib/libensem3a_rt.so``.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -19,7 +20,6 @@ LIB = os.path.join(LIBDIR, "libensem3a_rt.so")
 OBJDIR = os.path.join(ROOT, "build", "native")
 
 SOURCES = ["rt_kernels.hip", "rt_accum.hip", "rt_adaptive.hip", "rt_spec.hip", "rt_api.hip", "scene_pack.cpp", "bvh_build.cpp", "bvh_sah.cpp", "obj_load.cpp"]
-HEADERS = ["rt_kernels.hip", "rt_internal.h", "rt_layout.h", "scene_pack.h", "rt_device.h", "rtm.h", "bvh_sah.h"]
 # -ffp-contract=off: the numerics contract (rtm.h) places every fused multiply-add explicitly.
 COMMON = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-Wall",
           "-Wno-unused-function", "-I", os.path.join(ROOT, "include")]
@@ -46,8 +46,9 @@ def build(verbose: bool = False, force: bool = False, defines=(), out: str = Non
     objdir = OBJDIR if not defines else os.path.join(OBJDIR, "v_" + "_".join(d.replace("=", "") for d in defines))
     os.makedirs(objdir, exist_ok=True)
     os.makedirs(os.path.dirname(lib_path), exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", h)
-                                                      for h in ("rt_api.h", "rt_debug.h", "rt_scene.h")]
+    # every header present, and rt_kernels.hip, which rt_accum.hip and rt_adaptive.hip compile again
+    hdrs = (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")) +
+            [os.path.join(CSRC, "rt_kernels.hip")])
     jobs = []
     objs = []
     for src in SOURCES:

@@ -38,7 +38,7 @@ EXPORTED = (
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
-    "rt_debug_brute_refill", "rt_debug_last_refill",
+    "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
@@ -149,6 +149,7 @@ def lib():
             "rt_debug_last_slices": (_i32, []),
             "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
             "rt_debug_last_refill": (_i32, [_c_p]),
+            "rt_debug_last_launch": (_i32, [_c_p]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
@@ -602,6 +603,22 @@ def last_refill():
     if st != 0:
         raise NativeError(st, "rt_debug_last_refill: bad arguments")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide", "brute", "ts", "acc",
+                 "team", "walk_team", "slices", "refill", "grid", "lds")
+BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
+BRUTE_REFILL = 8
+
+
+def last_launch() -> dict:
+    """rt_debug_last_launch (include/rt_debug.h): the kernel key of the last render launch and the team sizes,
+    slice word, refill threshold, grid and LDS bytes its kernel got, by name (``LAUNCH_FIELDS``)."""
+    out = np.zeros(len(LAUNCH_FIELDS), np.int32)
+    st = lib().rt_debug_last_launch(out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_debug_last_launch: bad arguments")
+    return {name: int(v) for name, v in zip(LAUNCH_FIELDS, out)}
 
 
 def tile_rows(npix: int, width: int, row0: int, row_step: int) -> int:

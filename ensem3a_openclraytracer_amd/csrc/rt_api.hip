@@ -231,7 +231,7 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.ibl_sum = (const uint32_t*)d.ibl_sum.p;
     s.ibl_w = ctx->ibl_w;
     s.ibl_h = ctx->ibl_h;
-    // stack sized for whichever layout the launch picks (launch_fast uses the wide one only for the
+    // stack sized for whichever layout the launch picks (choose_kernel takes the wide one only for the
     // resumable walk of scenes not staged in LDS)
     s.depth = wide ? std::max(ctx->hs.depth, ctx->hs.wdepth) : ctx->hs.depth;
     s.brute = (const float4*)d.brute.p;
@@ -289,7 +289,7 @@ int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, i
     fp->spec_log = nullptr;
     fp->spec_cap = 0;
     fp->slices = 0;
-    fp->refill = ctx->brute_refill;   // the option: launch_t makes R of it (rt_internal.h brute_refill_launch)
+    fp->refill = ctx->brute_refill;   // the option: launch_pick makes R of it (rt_internal.h brute_refill_launch)
     fp->slice_state = nullptr;
     fp->slice_ready = nullptr;
     fp->pilot_cost = nullptr;
@@ -716,7 +716,7 @@ namespace {
 hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t s, int accum_base = -1) {
     fp.slices = 0;
     // brute-force scenes (the one-lane kernels, render_kernel): one-pass launches; K on auto is handed on as
-    // -K, and the launch decides where it knows its kernel's resident lanes (rt_kernels.hip launch_t), which
+    // -K, and the launch decides where it knows its kernel's resident lanes (rt_kernels.hip launch_pick), which
     // also zeroes the samples-done words when it takes slices
     const bool brute = ctx->hs.nbrute > 0;
     if (effective_traversal(ctx) != RT_TRAVERSAL_FAST || fp.nloc <= 0 || ctx->slices == 0 ||
@@ -1639,7 +1639,17 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
     return RT_OK;
 }
 
-int rt_debug_last_slices(void) { return rt::last_launch_slices(); }
+int rt_debug_last_slices(void) { return rt::last_launch().slices; }
+
+int rt_debug_last_launch(int32_t out[17]) {
+    if (!out) return RT_ERR_ARG;
+    const rt::LaunchNote n = rt::last_launch();
+    const rt::KernelKey& k = n.key;
+    const int64_t v[17] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
+                           k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds};
+    for (int i = 0; i < 17; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    return RT_OK;
+}
 
 int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out) {
     if (!out || nloc < 0 || lanes < 0 || option < -1 || option > rt::kRefillMax) return RT_ERR_ARG;
@@ -1649,7 +1659,7 @@ int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out)
 
 int rt_debug_last_refill(int64_t out[3]) {
     if (!out) return RT_ERR_ARG;
-    out[0] = rt::last_launch_refill();
+    out[0] = rt::last_launch().refill;
     out[1] = g_refill_events.load(std::memory_order_relaxed);
     out[2] = g_refill_lanes.load(std::memory_order_relaxed);
     return RT_OK;

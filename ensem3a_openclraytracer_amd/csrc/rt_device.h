@@ -589,7 +589,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         if constexpr (kBoxGroup > 2) if (rem & 2) group(IntC<2>{}, cb, g0 + (rem & ~3), ge);
         if constexpr (kBoxGroup > 1) if (rem & 1) group(IntC<1>{}, cb, g0 + (rem & ~1), ge);
     };
-    // (CLU kernels are launched for clustered scenes only, launch_t: they carry no loop over brute_box)
+    // (CLU kernels are launched for clustered scenes only, launch_pick: they carry no loop over brute_box)
     if (CLU) {
         float* inv = reinterpret_cast<float*>(wl + BRUTE_INV_OFF);                          // [3][64]
         unsigned* olist = reinterpret_cast<unsigned*>(wl + BRUTE_INV_OFF + 64 * 3 * 4);    // [BRUTE_OWNERS]
@@ -739,6 +739,36 @@ __host__ __device__ inline LaunchConst make_const(const FrameParams& F) {
 
 __global__ void make_const_kernel(FrameParams F, LaunchConst* __restrict__ out) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *out = make_const(F);
+}
+
+// Dynamic LDS of a block of the tree-walk and REF kernels: the per-lane stack, one column per work-item (FAST:
+// int2 entries; a brute-force scene walked without its staged copy needs no stack but the waves' batch area)
+inline size_t stack_lds_bytes(const DevScene& sc, int traversal, int block) {
+    const int depth = traversal == TRAV_REF ? sc.ref_stack : (sc.nbrute > 0 ? 1 : 2 * std::max(sc.stack_lds, 1));
+    const size_t lds = (size_t)depth * block * sizeof(int);
+    return traversal == TRAV_FAST && sc.nbrute > 0 ? std::max(lds, (size_t)(block / 64) * BRUTE_WAVE_LDS) : lds;
+}
+// ... of the brute-force kernels (BRUTE_ != 0), which stage the scene: records, boxes, shading, materials, clusters
+inline size_t brute_lds_bytes(const DevScene& sc, int block) {
+    return (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.nbox * 32 +
+           (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32;
+}
+// ... and what the SMEM walks stage behind their stack: the BVH2 nodes and the triangles
+inline size_t staged_scene_bytes(const DevScene& sc) {
+    return (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
+}
+
+// The work block before a render launch: the hand-out counters zeroed, the launch's constants behind them
+inline hipError_t setup_work_block(const FrameParams& f, unsigned int* d_work, hipStream_t stream,
+                                   const LaunchConst** lconst) {
+    static_assert(kConstOffset >= kGroups * kCounterStride && kConstOffset + sizeof(LaunchConst) <= kWorkBytes,
+                  "work block layout");
+    const hipError_t e = hipMemsetAsync(d_work, 0, (size_t)kGroups * kCounterStride, stream);
+    if (e != hipSuccess) return e;
+    LaunchConst* lc = reinterpret_cast<LaunchConst*>(reinterpret_cast<char*>(d_work) + kConstOffset);
+    hipLaunchKernelGGL(make_const_kernel, dim3(1), dim3(64), 0, stream, f, lc);
+    *lconst = lc;
+    return hipGetLastError();
 }
 
 // ---- camera ray direction, Raytracing.cl:18-37 ----
@@ -1598,7 +1628,7 @@ __device__ __forceinline__ int wide_node(float4 g0, float4 g1, float4 g2, float4
     // bound (rt_api.hip emit_wide), which exceeds the rounding of the two forms, 2^-24 (|p - o| +
     // |p + q s - o| + |b - o|) for a leaf bound b below, for every ray origin up to DevScene::wdq_omax
     // (~20 P): a child box never rejects what a leaf below it accepts; q = 0 is fl(p - o) in both
-    // forms.  launch_fast picks DQ per frame (hit points are within P; the camera is checked).
+    // forms.  choose_kernel picks DQ per frame (hit points are within P; the camera is checked).
     const float px = g0.x - R.o.x, py = g0.y - R.o.y, pz = g0.z - R.o.z;
 #pragma unroll
     for (int i = PRE0 ? 1 : 0; i < 4; ++i) {

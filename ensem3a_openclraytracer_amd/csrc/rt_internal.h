@@ -27,7 +27,7 @@ struct DevScene {
     int32_t wroot_ref;
     // every quantised child bound with q > 0 lies 2^-17 P outside its exact bound (rt_api.hip emit_wide),
     // which makes the origin-folded dequantisation conservative for ray origins with |o| <= wdq_omax
-    // (about 20 P; 0: no gap, exact form only); launch_fast checks the camera against it per frame
+    // (about 20 P; 0: no gap, exact form only); choose_kernel checks the camera against it per frame
     float wdq_omax;
     float root_box[6];     // min.xyz, max.xyz of the root
     // REF traversal: the reference's own AoS export, 9 floats per node
@@ -80,7 +80,7 @@ struct DevScene {
     const float4* brute_cbox;
     const float4* brute_crow;
     int32_t ncluster, ncslot, nsingle4;
-    int32_t cluster_auto;   // option "brute_cluster" is -1: launch_t clusters only tiles of at least a pixel per resident lane
+    int32_t cluster_auto;   // option "brute_cluster" is -1: launch_pick clusters only tiles of at least a pixel per resident lane
     // the real single slots at the head of brute_cbox.  The clustered loop tests slots [0, nsingle) and, where a
     // cluster runs lock-step, its `count` boxes in whole groups of kBoxGroup and then the last 1..3 alone: the
     // padding slots stay in memory -- a group load never leaves the buffer, an item's slot index is a shift and
@@ -150,7 +150,7 @@ struct FrameParams {
     // continues from the state.  Every pixel's samples run in order: the frame is the one-pass frame.
     // Brute-force scenes (the one-lane kernels, one-pass launches; the three forms of this word are made in one
     // place, rt_slices.h brute_slice_offer / brute_slice_launch): rt_api.hip hands K on, or -K for K on auto;
-    // launch_t decides from its kernel's resident lanes and gives the kernel K | tail << 8 -- only the last
+    // launch_pick decides from its kernel's resident lanes and gives the kernel K | tail << 8 -- only the last
     // tail / 256 of the tile's pixels are sliced, the others are whole jobs handed out first (take_job) -- and
     // the state is 48 bytes per pixel (+ the camera ray's direction; tc shares its word with the cached
     // shadow-ray hit).
@@ -243,13 +243,12 @@ constexpr int kWalkLanesPerCu = 4 * 4 * 64;
 size_t spec_log_bytes(const FrameParams& fp, int cus);
 hipError_t launch_spec(const DevScene& sc, const FrameParams& fp, int block, float* d_out, unsigned int* d_work,
                        hipStream_t stream);
-bool spec_walk(const DevScene& sc, const FrameParams& fp);
-// The host's rule for FrameParams::refill (option "brute_refill": -1 auto, 0 or 1 off, R >= 2 set).  launch_t
+// The host's rule for FrameParams::refill (option "brute_refill": -1 auto, 0 or 1 off, R >= 2 set).  launch_pick
 // applies it where it knows its kernel's resident lanes; rt_debug_brute_refill evaluates it for
 // tests/test_brute_refill_rule.py (no frame depends on it).  Auto: R = kRefillBrute on tiles of at least 1.5
 // pixels per resident lane (the boundary of the sample slices, rt_slices.h: below it the waves run half empty
 // and a waiting lane is a larger share of the work), off elsewhere -- such a launch runs the kernels without the
-// threshold's code (launch_t).  C2 (r12; ms per frame, the parent 6.45): R = 1 / 4 / 6 / 8 / 16
+// threshold's code (launch_pick).  C2 (r12; ms per frame, the parent 6.45): R = 1 / 4 / 6 / 8 / 16
 // 6.48-6.52 / 6.28-6.30 / 6.27-6.29 / 6.28-6.31 / 6.54; rows 0::2 (1.6 pixels per lane) 3.74 -> 3.64
 constexpr int kRefillBrute = 4;
 constexpr int kRefillMax = 64;
@@ -257,14 +256,47 @@ inline int brute_refill_launch(int option, int64_t nloc, int64_t lanes) {
     if (option >= 0) return option >= 2 ? (int)std::min<int64_t>(option, kRefillMax) : 0;
     return brute_auto_slices(nloc, lanes) ? kRefillBrute : 0;
 }
+// Which instantiation of render_kernel / render_resume_kernel a launch runs, as named fields (rt_kernels.hip:
+// choose_kernel makes the scene- and frame-level choice, launch_pick refines it with the tile-level rules and
+// looks the kernel up in its translation unit's table).  The fields are the kernels' template arguments.
+struct KernelKey {
+    int trav;     // TRAV_FAST, TRAV_REF
+    int count;    // instrumented (rt_count_work*)
+    int log;      // debug event log of one pixel
+    int smem;     // tree walk with the scene staged in LDS
+    int ovf;      // tree walk whose stack spills to DevScene::stack_ovf
+    int resume;   // render_resume_kernel (the resumable tree walk); 0: render_kernel
+    int step;     // resumable walk: one item per traversal step (0: descend-until-leaf rounds)
+    int wide;     // resumable walk: 0 BVH2, 1 the 4-wide layout, 2 ... with origin-folded dequantisation
+    int brute;    // render_kernel's BRUTE_: 0 none, 1 lock-step, 2 teams, 3 clustered, | kBruteSliced | kBruteRefill
+    int ts;       // resumable walk: lanes per pixel (1, 2, 4, 8)
+    int acc;      // 0 one-shot, kAccAdd, kAccListed
+};
+inline bool operator==(const KernelKey& a, const KernelKey& b) {
+    return a.trav == b.trav && a.count == b.count && a.log == b.log && a.smem == b.smem && a.ovf == b.ovf &&
+           a.resume == b.resume && a.step == b.step && a.wide == b.wide && a.brute == b.brute && a.ts == b.ts &&
+           a.acc == b.acc;
+}
+// The engine of a pass over (sc, fp): REF, brute force, the plain, LDS-staged or overflow tree walk, the
+// resumable walk with its step and layout.  Pure: no device call.  brute is 0 or 1 and ts 1 here; the tile
+// decides the rest (launch_pick).
+KernelKey choose_kernel(const DevScene& sc, const FrameParams& fp, int traversal, bool count, bool log, int acc,
+                        int block);
+// Blocks of fn (block threads, lds bytes of dynamic LDS) the current device keeps resident, at most max_waves
+// waves per SIMD (0: no cap); 0 and *err set when the query fails or fn is null.  Each (device, fn, block, lds)
+// is queried once: the host query costs more than a launch.
+int64_t resident_blocks(const void* fn, int block, size_t lds, int max_waves, hipError_t* err);
 // test hooks
-// FrameParams::refill as the kernel of the last launch_t got it (0: every lane refilled at once), and the refill
-// counters of the last instrumented launch (count_all)
-void note_launch_refill(int v);
-int last_launch_refill();
-// FrameParams::slices as the kernel of the last launch_t got it (0: an unsliced launch)
-void note_launch_slices(int v);
-int last_launch_slices();
+// The process's last render launch (launch_pick) as its kernel got it: the refined key, FrameParams::team,
+// walk_team, slices and refill (0: every lane refilled at once), the grid and the dynamic LDS bytes
+struct LaunchNote {
+    KernelKey key;
+    int team, walk_team, slices, refill;
+    int64_t grid;
+    size_t lds;
+};
+void note_launch(const LaunchNote& n);
+LaunchNote last_launch();
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream);
 hipError_t launch_debug_log(const DevScene& sc, const FrameParams& fp, int traversal, float* d_out,
                             unsigned int* d_work, hipStream_t stream);

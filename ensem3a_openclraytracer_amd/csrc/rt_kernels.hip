@@ -24,7 +24,8 @@
 //
 // Numerics: every OpenCL builtin of the reference is taken from rtm.h and the
 // file is compiled with -ffp-contract=off (see rtm.h).
-#include <atomic>
+#include <mutex>
+#include <vector>
 
 #include "rt_device.h"
 
@@ -191,7 +192,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     // F.slices = K | tail << 8: only the last tail / 256 of the pixels are sliced, the rest are whole jobs handed
     // out before them (take_pixel), so the hand-offs are paid where the frame ends and nowhere else.
     // The hand-off carries sun0 beside tc (16 bits each: the scene is staged in LDS, ntri + 2 < 2^16,
-    // launch_t), so a pixel traces its first bounce's shadow ray once, not once per slice, and the camera
+    // launch_pick), so a pixel traces its first bounce's shadow ray once, not once per slice, and the camera
     // ray's direction: a job that continues a pixel divides nothing and runs no camera_dir (with a job
     // ending in nearly every round of a wave, that start-up is run by the whole wave every round)
     const unsigned nsl = SLICED ? (unsigned)F.slices & 0xffu : 1u;
@@ -258,7 +259,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                     i = (int)i64;
                 }
                 if (ok) {
-                    if constexpr (SLICED) {   // i < npix = imgSize (ok above; npix < 2^31, launch_t): no division
+                    if constexpr (SLICED) {   // i < npix = imgSize (ok above; npix < 2^31, launch_pick): no division
                         seed0 = (uint32_t)i;
                         seed1 = 0;
                     } else {
@@ -537,7 +538,7 @@ constexpr size_t kStepMaxBytes = 16u << 20;
 
 // TS > 1: teams of TS lanes per pixel walk each ray together (team_step; BVH2 item steps only).
 // WIDE: 0 = the BVH2 walk, 1 = the 4-wide walk, 2 = the 4-wide walk with origin-folded dequantisation
-// (wide_node DQ; launch_fast picks it when the camera lies within DevScene::wdq_omax)
+// (wide_node DQ; choose_kernel picks it when the camera lies within DevScene::wdq_omax)
 template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS = 1, int ACC = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? kWideWaves : 4))) render_resume_kernel(DevScene S, FrameParams F, float* __restrict__ out,
                                                       unsigned long long* __restrict__ counts,
@@ -1036,182 +1037,79 @@ __global__ void pilot_team_pick_kernel(const unsigned* __restrict__ left, int64_
     }
 }
 
-template <int TRAV, bool COUNT, bool LOG, bool SMEM = false, bool RESUME = false, bool OVF = false,
-          bool BRUTE = false, bool STEP = true, int WIDE = 0, int ACC = 0>
-hipError_t launch_t(const DevScene& sc, const FrameParams& fp, int block, float* d_out, unsigned long long* d_counts,
-                    unsigned int* d_work, hipStream_t stream) {
-    // FAST: int2 entries; the brute-force path of small scenes needs no stack
-    const int depth = (TRAV == TRAV_REF) ? sc.ref_stack : (sc.nbrute > 0 ? 1 : 2 * (sc.stack_lds > 0 ? sc.stack_lds : 1));
-    size_t lds = (size_t)depth * block * sizeof(int);
-    if (TRAV == TRAV_FAST && sc.nbrute > 0) lds = std::max(lds, (size_t)(block / 64) * BRUTE_WAVE_LDS);
-    if (BRUTE)
-        lds = (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.nbox * 32 +
-              (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32;
-    if (SMEM) lds += (size_t)(kNodeF4 * sc.nnodes + 3 * sc.ntri) * sizeof(float4);
-    if (fp.nloc <= 0) return hipSuccess;
-    // persistent grid: as many blocks as the device keeps resident (pixels are handed out by d_work)
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // clustered scenes (DevScene::ncluster > 0) run the one-lane product kernel with the clustered loop (BRUTE = 3);
-    // the instrumented build and every other scene keep the lock-step loop over brute_box (BRUTE = 1)
-    constexpr int kBruteClu = (BRUTE && !COUNT && !LOG) ? 3 : BRUTE ? 1 : 0;
-    bool clu = kBruteClu == 3 && sc.ncluster > 0;
-    const void* kfn = RESUME ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>
-                             : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>;
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, block, lds);
-    if (e != hipSuccess) return e;
-    // auto: only tiles with at least one pixel per resident lane.  Measured on C2 (DESIGN.md 5.2): the whole
-    // frame (3.2 pixels per lane) 7.29 -> 7.02 ms, the 1/8 tile (0.4 per lane: half-empty waves that wait on
-    // the LDS round trips of the item batches instead of on VALU issue) 2.14 -> 2.23 ms
-    if (clu && sc.cluster_auto &&
-        fp.nloc < (int64_t)std::max(1, cus) * std::max(1, per_cu) * block)
-        clu = false;
-    if (clu) {
-        kfn = (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu, ACC>;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, block, lds);
-        if (e != hipSuccess) return e;
+// ---- the kernel table of this translation unit: every instantiation it holds, by key ----
+// rt_kernels.hip holds the one-shot kernels (product, instrumented, logging), rt_accum.hip the adds' and
+// rt_adaptive.hip the listed adds' (product only).  The product kernels' instruction streams move with their
+// module's contents: a row added here is a change to every kernel of the module.
+#ifdef RT_ACCUM_TU
+constexpr int kTuAcc = RT_ACCUM_TU;
+#else
+constexpr int kTuAcc = 0;
+#endif
+struct KernelRow {
+    KernelKey key;
+    const void* fn;
+};
+// A row's key is made from the template arguments that name its kernel: the two cannot disagree.
+template <int TRAV, bool COUNT, bool LOG, bool SMEM, bool OVF, int BRUTE_>
+KernelRow render_row() {
+    return {KernelKey{TRAV, COUNT, LOG, SMEM, OVF, 0, 1, 0, BRUTE_, 1, kTuAcc},
+            (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE_, kTuAcc>};
+}
+template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS>
+KernelRow walk_row() {
+    return {KernelKey{TRAV_FAST, COUNT, LOG, SMEM, OVF, 1, STEP, WIDE, 0, TS, kTuAcc},
+            (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, TS, kTuAcc>};
+}
+// The module holds its kernels in the order this file first names them -- the order of the rows -- and the product
+// kernels' code moves with that order too (tools/code_object_diff.py shows it).  Hence this order:
+// what the product and the instrumented kernels both have, the one-lane item-step walk and REF ...
+template <bool COUNT>
+void head_rows(std::vector<KernelRow>& t) {
+    t.push_back(walk_row<COUNT, false, false, false, true, 0, 1>());
+    t.push_back(render_row<TRAV_REF, COUNT, false, false, false, 0>());
+}
+// ... the 4-wide walk in rounds, the plain tree walk, the wide item steps origin-folded and exact ...
+template <bool COUNT, bool OVF>
+void wide_rows(std::vector<KernelRow>& t) {
+    t.push_back(walk_row<COUNT, false, false, OVF, false, 1, 1>());
+    t.push_back(render_row<TRAV_FAST, COUNT, false, false, OVF, 0>());
+    t.push_back(walk_row<COUNT, false, false, OVF, true, 2, 1>());
+    t.push_back(walk_row<COUNT, false, false, OVF, true, 1, 1>());
+}
+// ... the item-step teams of one stack / staging form
+template <bool COUNT, bool SMEM, bool OVF>
+void team_rows(std::vector<KernelRow>& t) {
+    t.push_back(walk_row<COUNT, false, SMEM, OVF, true, 0, 2>());
+    t.push_back(walk_row<COUNT, false, SMEM, OVF, true, 0, 4>());
+    t.push_back(walk_row<COUNT, false, SMEM, OVF, true, 0, 8>());
+}
+// ... and the staged walks, the teams, the BVH2 walk in rounds, brute force lock-step, in teams and sliced.
+// Product only: the clustered loop (3) and the refill forms (COUNT and LOG carry the threshold without the flag).
+template <bool COUNT>
+void engine_rows(std::vector<KernelRow>& t) {
+    wide_rows<COUNT, true>(t);
+    wide_rows<COUNT, false>(t);
+    t.push_back(walk_row<COUNT, false, true, false, true, 0, 1>());
+    t.push_back(render_row<TRAV_FAST, COUNT, false, true, false, 0>());
+    team_rows<COUNT, true, false>(t);
+    t.push_back(walk_row<COUNT, false, false, true, true, 0, 1>());
+    team_rows<COUNT, false, true>(t);
+    team_rows<COUNT, false, false>(t);
+    t.push_back(walk_row<COUNT, false, true, false, false, 0, 1>());
+    t.push_back(walk_row<COUNT, false, false, true, false, 0, 1>());
+    t.push_back(walk_row<COUNT, false, false, false, false, 0, 1>());
+    t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 1>());
+    if constexpr (!COUNT) t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 3>());
+    t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 2>());
+    if constexpr (!COUNT) t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 3 | kBruteSliced>());
+    t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 1 | kBruteSliced>());
+    if constexpr (!COUNT) {
+        t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 3 | kBruteSliced | kBruteRefill>());
+        t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 1 | kBruteSliced | kBruteRefill>());
+        t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 3 | kBruteRefill>());
+        t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 1 | kBruteRefill>());
     }
-    // blocks per CU for at most max_waves waves per SIMD (4 SIMDs per CU)
-    const int cap_cu = fp.max_waves > 0 ? std::max(1, fp.max_waves * 4 * 64 / block) : INT_MAX;
-    const int64_t resident = (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu, cap_cu));
-    // sample slices of the one-lane brute-force kernels (rt_api.hip setup_slices: fp.slices = K, or -K for K
-    // on auto, decided here where the resident lanes are known: rt_slices.h brute_slice_launch): one-pass
-    // launches only, and no teams -- a set slice count keeps a tile the team rule would take on single lanes.
-    // bslices: FrameParams::slices as the sliced kernels read it, K | tail << 8 (a set slice count slices every
-    // pixel, auto only the tile's last pixels), 0 for an unsliced launch
-    int bslices = 0;
-    if (BRUTE && !RESUME && ACC != kAccListed && fp.pass == 0 && fp.team <= 1 && fp.slice_state && fp.slice_ready && sc.ntri + 2 < 65536 &&
-        fp.npix <= INT_MAX)
-        bslices = brute_slice_launch(fp.slices, fp.nloc, resident * block);
-    constexpr int kBruteSl = BRUTE ? (kBruteClu | kBruteSliced) : 0;   // clustered or not, as above
-    constexpr int kBruteSl1 = BRUTE ? (1 | kBruteSliced) : 0;
-    // the product kernels with a refill threshold are instantiations of their own (the instrumented and logging
-    // ones carry its code anyway)
-    constexpr int kBruteRf = (BRUTE && !RESUME && !COUNT && !LOG) ? kBruteRefill : 0;
-    // team walk (render_resume_kernel TEAM): BVH2 item steps only; walk_team, 0 = auto (auto_walk_team;
-    // pass 2 of a pilot launch: the size pilot_team_pick_kernel chose, launch_render)
-    constexpr bool kTeamable = RESUME && STEP && !WIDE && !LOG;
-    int wteam = 1;
-    if (kTeamable) {
-        wteam = fp.walk_team;
-        // (a listed add: the list's length is known on the device only -- one lane per pixel unless teams are set)
-        if (wteam == 0) wteam = ACC == kAccListed ? 1 : auto_walk_team(fp.nloc, resident * block);
-        if (wteam != 2 && wteam != 4 && wteam != 8) wteam = 1;
-    }
-
-    // brute-force teams: a tile with fewer pixels than the device has lanes (a row slice of a
-    // multi-GPU frame) gives each pixel 4 lanes that split its box tests when it fills at most a quarter of them
-    FrameParams f = fp;
-    f.team = 1;
-    if (BRUTE) {
-        f.team = fp.team;
-        if (bslices) f.team = 1;
-        if (f.team == 0) {
-            // measured on C2 tiles (one MI355X, 96-VGPR kernel: 327,680 resident lanes): a 1/8 tile
-            // (131k pixels) is fastest with single lanes (2.23 vs 2.29 ms with pairs), a 1/16 tile with
-            // teams of 4 (1.67 vs 1.88 with pairs, 2.28 single)
-            const int64_t lanes = resident * block;
-            f.team = (ACC != kAccListed && fp.nloc * 4 <= lanes) ? 4 : 1;   // (a listed add: as for wteam above)
-        }
-    }
-    f.walk_team = wteam;
-    // the refill threshold of the one-lane brute-force kernels (fp.refill: the option; f.refill: R, or 0), from
-    // the resident lanes of the kernel picked above (the sliced instantiations keep the same five waves)
-    f.refill = (BRUTE && !RESUME && f.team <= 1) ? brute_refill_launch(fp.refill, fp.nloc, resident * block) : 0;
-    note_launch_refill(f.refill);   // (rt_debug_last_refill)
-    const int64_t need = (fp.nloc * f.team * wteam + block - 1) / block;
-    int64_t grid = std::min(need, resident);
-    // the team instantiations (TS = 2, 4, 8) and their own occupancy
-    auto team_fn = [&](int ts) -> const void* {
-        if (!kTeamable) return nullptr;
-        return ts == 2 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1, ACC>
-             : ts == 4 ? (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1, ACC>
-                       : (const void*)render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1, ACC>;
-    };
-    auto team_grid = [&](int ts, int64_t* g) -> hipError_t {
-        int per_cu_w = 0;
-        hipError_t er = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_w, team_fn(ts), block, lds);
-        *g = std::min((fp.nloc * ts + block - 1) / block,
-                      (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu_w, cap_cu)));
-        return er;
-    };
-    if (kTeamable && wteam > 1) {
-        e = team_grid(wteam, &grid);
-        if (e != hipSuccess) return e;
-    }
-    // teams run their own instantiation (the ts = 1 kernel keeps the scalar box loop)
-    const void* tfn = (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>;
-    if (BRUTE && f.team > 1) {
-        int per_cu_t = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_t, tfn, block, lds);
-        if (e != hipSuccess) return e;
-        grid = std::min(need, (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu_t, cap_cu)));
-    }
-    // the sliced instantiations and their own occupancy: the grid stays within what the device keeps resident
-    // (not that the hand-off needs it: a job is only ever held by a wave that is running, and the job of a
-    // pixel's slice k is taken before that of its slice k + 1, so a waiting lane's chain ends in a running one)
-    const void* sfn = clu ? (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl, ACC>
-                          : (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1, ACC>;
-    if (!RESUME) f.slices = bslices;
-    note_launch_slices(f.slices);   // (rt_debug_last_slices)
-    if (bslices) {
-        int per_cu_s = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, sfn, block, lds);
-        if (e != hipSuccess) return e;
-        grid = std::min(need, (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu_s, cap_cu)));
-        // the samples-done words of the tile's pixels (the tree walk's are zeroed by setup_slices)
-        e = hipMemsetAsync(f.slice_ready, 0, (size_t)fp.nloc * sizeof(uint32_t), stream);
-        if (e != hipSuccess) return e;
-    }
-    e = hipMemsetAsync(d_work, 0, (size_t)kGroups * kCounterStride, stream);
-    if (e != hipSuccess) return e;
-    // the per-launch constants live after the counters in the same scratch block
-    static_assert(kConstOffset >= kGroups * kCounterStride && kConstOffset + sizeof(LaunchConst) <= kWorkBytes,
-                  "work block layout");
-    LaunchConst* lc = reinterpret_cast<LaunchConst*>(reinterpret_cast<char*>(d_work) + kConstOffset);
-    hipLaunchKernelGGL(make_const_kernel, dim3(1), dim3(64), 0, stream, f, lc);
-    if (kTeamable && wteam == 2)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 2 : 1, ACC>),
-                           dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
-                           (const LaunchConst*)lc);
-    else if (kTeamable && wteam == 4)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 4 : 1, ACC>),
-                           dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
-                           (const LaunchConst*)lc);
-    else if (kTeamable && wteam == 8)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, kTeamable ? 8 : 1, ACC>),
-                           dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
-                           (const LaunchConst*)lc);
-    else if (RESUME)
-        hipLaunchKernelGGL((render_resume_kernel<COUNT, LOG, SMEM, OVF, STEP, WIDE, 1, ACC>), dim3((unsigned)grid), dim3(block), lds, stream,
-                           sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else if (kBruteRf && f.refill > 1) {
-        // the instantiations with the refill threshold (same registers and LDS as their twins below: the grid stands)
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, stream, sc, f, d_out, d_counts, d_work,
-                               (const LaunchConst*)lc);
-        };
-        if (bslices && clu) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl | kBruteRf, ACC>);
-        else if (bslices) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1 | kBruteRf, ACC>);
-        else if (clu) go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu | kBruteRf, ACC>);
-        else go(render_kernel<TRAV, COUNT, LOG, SMEM, OVF, (BRUTE ? 1 : 0) | kBruteRf, ACC>);
-    } else if (BRUTE && bslices && clu)
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl, ACC>), dim3((unsigned)grid),
-                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else if (BRUTE && bslices)
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteSl1, ACC>), dim3((unsigned)grid),
-                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else if (BRUTE && f.team > 1)
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 2 : 0, ACC>), dim3((unsigned)grid),
-                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else if (clu)
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, kBruteClu, ACC>), dim3((unsigned)grid),
-                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    else
-        hipLaunchKernelGGL((render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE ? 1 : 0, ACC>), dim3((unsigned)grid),
-                           dim3(block), lds, stream, sc, f, d_out, d_counts, d_work, (const LaunchConst*)lc);
-    return hipGetLastError();
 }
 
 // ---- test hooks (rt_debug.h): device evaluation of the numerics contract and of
@@ -1260,13 +1158,45 @@ __global__ void __launch_bounds__(256) debug_trace_kernel(DevScene S, const floa
 // object of this one -- every one-shot kernel -- is built from exactly what it was built from without them
 // (rt_adaptive.hip, RT_ACCUM_TU 2, does the same for the listed instantiations: launch_accum_listed, below)
 #ifndef RT_ACCUM_TU
-// FrameParams::slices as the last launch's kernel got it (rt_debug_last_slices: which kernel a test launched)
-static std::atomic<int> g_last_slices{0};
-void note_launch_slices(int v) { g_last_slices.store(v, std::memory_order_relaxed); }
-int last_launch_slices() { return g_last_slices.load(std::memory_order_relaxed); }
-static std::atomic<int> g_last_refill{0};
-void note_launch_refill(int v) { g_last_refill.store(v, std::memory_order_relaxed); }
-int last_launch_refill() { return g_last_refill.load(std::memory_order_relaxed); }
+// the last launch_pick of any of the three translation units (rt_debug_last_launch: which kernel a test launched)
+static std::mutex g_note_mu;
+static LaunchNote g_note{};
+void note_launch(const LaunchNote& n) {
+    std::lock_guard<std::mutex> g(g_note_mu);
+    g_note = n;
+}
+LaunchNote last_launch() {
+    std::lock_guard<std::mutex> g(g_note_mu);
+    return g_note;
+}
+
+int64_t resident_blocks(const void* fn, int block, size_t lds, int max_waves, hipError_t* err) {
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t e = fn ? hipGetDevice(&dev) : hipErrorInvalidDeviceFunction;   // a kernel that is not built
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) {
+        // (a context may hold devices of different kinds)
+        struct Occ { int dev; const void* fn; int block; size_t lds; int per_cu; };
+        static std::mutex mu;
+        static std::vector<Occ> seen;
+        std::lock_guard<std::mutex> g(mu);
+        for (const Occ& o : seen)
+            if (o.dev == dev && o.fn == fn && o.block == block && o.lds == lds) per_cu = o.per_cu;
+        if (per_cu == 0) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, lds);
+            if (seen.size() >= 1024) seen.clear();   // (a process that renders very many scenes: lds varies)
+            if (e == hipSuccess) seen.push_back({dev, fn, block, lds, per_cu});
+        }
+    }
+    if (e != hipSuccess) {
+        *err = e;
+        return 0;
+    }
+    // blocks per CU for at most max_waves waves per SIMD (4 SIMDs per CU)
+    const int cap_cu = max_waves > 0 ? std::max(1, max_waves * 4 * 64 / block) : INT_MAX;
+    return (int64_t)std::max(1, cus) * std::max(1, std::min(per_cu, cap_cu));
+}
+
 
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, int64_t n, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
@@ -1274,13 +1204,19 @@ hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out,
     return hipGetLastError();
 }
 
-hipError_t launch_debug_log(const DevScene& sc, const FrameParams& fp, int traversal, float* d_out,
-                            unsigned int* d_work, hipStream_t stream) {
-    if (traversal == TRAV_REF) return launch_t<TRAV_REF, false, true>(sc, fp, 64, d_out, nullptr, d_work, stream);
-    if (sc.nbrute == 0 && sc.stack_lds < sc.depth)
-        return launch_t<TRAV_FAST, false, true, false, false, true>(sc, fp, 64, d_out, nullptr, d_work, stream);
-    return launch_t<TRAV_FAST, false, true>(sc, fp, 64, d_out, nullptr, d_work, stream);
+namespace {
+// The logging kernels' rows of the kernel table (below): REF and the plain walk with and without overflow (the two
+// resumable walks are never launched -- a log runs the plain walk -- but part of this module since the logging
+// launches named them).  They stand here, before launch_debug_trace, because the module holds its kernels in the
+// order this file first names them, and that order is part of the one-shot kernels' code (kernel_table).
+void log_rows(std::vector<KernelRow>& t) {
+    t.push_back(walk_row<false, true, false, false, true, 0, 1>());
+    t.push_back(render_row<TRAV_REF, false, true, false, false, 0>());
+    t.push_back(walk_row<false, true, false, true, true, 0, 1>());
+    t.push_back(render_row<TRAV_FAST, false, true, false, true, 0>());
+    t.push_back(render_row<TRAV_FAST, false, true, false, false, 0>());
 }
+}  // namespace
 
 hipError_t launch_ibl_sum(const uchar4* rgba, int w, int h, uint32_t* sum, hipStream_t stream) {
     const int64_t n = (int64_t)(w + 1) * (h + 1);
@@ -1304,9 +1240,7 @@ hipError_t launch_debug_trace(const DevScene& sc, int traversal, const float* ra
     DevScene s2 = sc;
     s2.stack_lds = sc.depth > 0 ? sc.depth : 1;
     s2.stack_ovf = nullptr;
-    const int depth = traversal == TRAV_REF ? s2.ref_stack : 2 * s2.stack_lds;
-    size_t lds = (size_t)depth * block * sizeof(int);
-    if (traversal != TRAV_REF && sc.nbrute > 0) lds = std::max(lds, (size_t)(block / 64) * BRUTE_WAVE_LDS);
+    const size_t lds = stack_lds_bytes(s2, traversal == TRAV_REF ? TRAV_REF : TRAV_FAST, block);
     if (traversal == TRAV_REF)
         hipLaunchKernelGGL(debug_trace_kernel<TRAV_REF>, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds,
                            stream, s2, rays, out, n);
@@ -1314,21 +1248,6 @@ hipError_t launch_debug_trace(const DevScene& sc, int traversal, const float* ra
         hipLaunchKernelGGL(debug_trace_kernel<TRAV_FAST>, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds,
                            stream, s2, rays, out, n);
     return hipGetLastError();
-}
-
-#endif  // !RT_ACCUM_TU
-
-template <bool COUNT, bool STEP, int ACC>
-hipError_t launch_resume(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
-                         unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, bool smem, bool ovf) {
-    if (smem)
-        return launch_t<TRAV_FAST, COUNT, false, true, true, false, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts,
-                                                                                 d_work, stream);
-    if (ovf)
-        return launch_t<TRAV_FAST, COUNT, false, false, true, true, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts,
-                                                                                 d_work, stream);
-    return launch_t<TRAV_FAST, COUNT, false, false, true, false, false, STEP, 0, ACC>(sc, fp, block, d_out, d_counts, d_work,
-                                                                              stream);
 }
 
 // A small tree-walk scene is staged in LDS (SMEM kernels).  Those kernels keep the whole stack in LDS too:
@@ -1341,55 +1260,135 @@ static bool stage_in_lds(const DevScene& sc) {
     return sc.ntri > 0 && sc.nbrute == 0 && scene_bytes <= kLdsSceneMax && sc.stack_lds >= sc.depth;
 }
 
-template <bool COUNT, int ACC = 0>
-hipError_t launch_fast(const DevScene& sc, const FrameParams& fp, int block, float* d_out,
-                       unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
-    const bool ovf = sc.nbrute == 0 && sc.stack_lds < sc.depth;
-    const bool smem = stage_in_lds(sc);
-    const bool resume = sc.ntri > 0 && sc.nbrute == 0 && fp.resume_min > 0;
-    const bool step = fp.step == 1 || (fp.step == 0 && (size_t)sc.nnodes * kNodeF4 * 16 <= kStepMaxBytes);
-    if (resume && fp.wide && sc.wnodes && !smem) {
-        // the wide walk takes item steps unless rounds are asked for (C5: 1,181 vs 1,035 Msamples/s);
-        // the item steps dequantise origin-folded (WIDE 2) when every ray origin of the frame is within
-        // the bound the builder's gap covers: hit points always are, the camera is checked here
-        const bool step = fp.step != 2;
-        // (each coordinate compared on its own: false for a NaN in any of them, which a std::max over the
-        // three would drop from its second operand)
-        const bool cam_in = std::fabs(fp.cam[0]) <= sc.wdq_omax && std::fabs(fp.cam[1]) <= sc.wdq_omax &&
-                            std::fabs(fp.cam[2]) <= sc.wdq_omax;
-        const bool dq = fp.wdq != 0 && sc.wdq_omax > 0.0f && cam_in;
-        if (ovf)
-            return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, false, 1, ACC>(
-                               sc, fp, block, d_out, d_counts, d_work, stream)
-                   : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 2, ACC>(
-                               sc, fp, block, d_out, d_counts, d_work, stream)
-                         : launch_t<TRAV_FAST, COUNT, false, false, true, true, false, true, 1, ACC>(
-                               sc, fp, block, d_out, d_counts, d_work, stream);
-        return !step ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, false, 1, ACC>(
-                           sc, fp, block, d_out, d_counts, d_work, stream)
-               : dq  ? launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 2, ACC>(
-                           sc, fp, block, d_out, d_counts, d_work, stream)
-                     : launch_t<TRAV_FAST, COUNT, false, false, true, false, false, true, 1, ACC>(
-                           sc, fp, block, d_out, d_counts, d_work, stream);
+KernelKey choose_kernel(const DevScene& sc, const FrameParams& fp, int traversal, bool count, bool log, int acc,
+                        int block) {
+    KernelKey k{traversal, count, log, /*smem*/ 0, /*ovf*/ 0, /*resume*/ 0, /*step*/ 1, /*wide*/ 0, /*brute*/ 0, /*ts*/ 1, acc};
+    if (traversal == TRAV_REF) return k;
+    k.ovf = sc.nbrute == 0 && sc.stack_lds < sc.depth;
+    if (log) return k;   // a log runs the plain walk (on a brute-force scene: its loop over the global records)
+    if (sc.ntri > 0 && sc.nbrute == 0 && fp.resume_min > 0) {
+        k.resume = 1;
+        if (fp.wide && sc.wnodes && !stage_in_lds(sc)) {
+            // the wide walk takes item steps unless rounds are asked for (C5: 1,181 vs 1,035 Msamples/s);
+            // the item steps dequantise origin-folded (2) when every ray origin of the frame is within
+            // the bound the builder's gap covers: hit points always are, the camera is checked here
+            // (each coordinate compared on its own: false for a NaN in any of them, which a std::max over the
+            // three would drop from its second operand)
+            const bool cam_in = std::fabs(fp.cam[0]) <= sc.wdq_omax && std::fabs(fp.cam[1]) <= sc.wdq_omax &&
+                                std::fabs(fp.cam[2]) <= sc.wdq_omax;
+            k.step = fp.step != 2;
+            k.wide = (k.step && fp.wdq != 0 && sc.wdq_omax > 0.0f && cam_in) ? 2 : 1;
+            return k;
+        }
+        k.step = fp.step == 1 || (fp.step == 0 && (size_t)sc.nnodes * kNodeF4 * 16 <= kStepMaxBytes);
+        k.smem = stage_in_lds(sc);   // (never with ovf: staged trees are no deeper than stack_lds)
+        return k;
     }
-    if (resume) {
-        return step ? launch_resume<COUNT, true, ACC>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf)
-                    : launch_resume<COUNT, false, ACC>(sc, fp, block, d_out, d_counts, d_work, stream, smem, ovf);
-    }
-    // BRUTE stages the scene in LDS: only while two blocks still fit a CU
-    const size_t brute_lds = (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 +
-                             (size_t)sc.nbox * 32 + (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) +
-                             (size_t)sc.ncslot * 32;
-    if (sc.ntri > 0 && sc.nbrute > 0 && brute_lds <= 80 * 1024)
-        return launch_t<TRAV_FAST, COUNT, false, false, false, false, true, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work,
-                                                                            stream);
-    if (smem) return launch_t<TRAV_FAST, COUNT, false, true, false, false, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
-    if (ovf)
-        return launch_t<TRAV_FAST, COUNT, false, false, false, true, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
-    return launch_t<TRAV_FAST, COUNT, false, false, false, false, false, true, 0, ACC>(sc, fp, block, d_out, d_counts, d_work, stream);
+    // brute force stages the scene in LDS: only while two blocks still fit a CU
+    if (sc.ntri > 0 && sc.nbrute > 0 && brute_lds_bytes(sc, block) <= 80 * 1024) k.brute = 1;
+    else k.smem = stage_in_lds(sc);
+    return k;
 }
 
+#endif  // !RT_ACCUM_TU
+
+namespace {
+// the instantiation a key names; nullptr: not built
+const void* kernel_fn(const KernelKey& k) {
+    static const std::vector<KernelRow> table = [] {
+        std::vector<KernelRow> t;
 #ifndef RT_ACCUM_TU
+        log_rows(t);
+        head_rows<true>(t);
+        head_rows<false>(t);
+        engine_rows<true>(t);
+#else
+        head_rows<false>(t);
+#endif
+        engine_rows<false>(t);
+        return t;
+    }();
+    for (const KernelRow& r : table)
+        if (r.key == k) return r.fn;
+    return nullptr;
+}
+
+// One pass: the engine choose_kernel picked, refined by the tile's rules in their order, each going by the resident
+// lanes of the kernel picked so far; then a persistent grid (pixels are handed out by d_work) of the kernel named
+hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, int block, float* d_out,
+                       unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    const bool brute = k.brute != 0, product = !k.count && !k.log, listed = k.acc == kAccListed;
+    const size_t lds = (brute ? brute_lds_bytes(sc, block) : stack_lds_bytes(sc, k.trav, block)) +
+                       (k.smem ? staged_scene_bytes(sc) : 0);
+    hipError_t e = hipSuccess;
+    // blocks the device keeps resident of the kernel k names now, at most max_waves waves per SIMD
+    auto resident = [&](int max_waves) { return resident_blocks(kernel_fn(k), block, lds, max_waves, &e); };
+    // clustered scenes (DevScene::ncluster > 0) run the one-lane product kernel with the clustered loop (3); the
+    // instrumented build and every other scene keep the lock-step loop over brute_box (1).
+    // auto: only tiles with at least one pixel per resident lane.  Measured on C2 (DESIGN.md 5.2): the whole
+    // frame (3.2 pixels per lane) 7.29 -> 7.02 ms, the 1/8 tile (0.4 per lane: half-empty waves that wait on
+    // the LDS round trips of the item batches instead of on VALU issue) 2.14 -> 2.23 ms
+    if (brute && product && sc.ncluster > 0 && !(sc.cluster_auto && fp.nloc < resident(0) * block)) k.brute = 3;
+    const int64_t lanes = resident(fp.max_waves) * block;
+    if (e != hipSuccess) return e;
+    FrameParams f = fp;
+    // sample slices of the one-lane brute-force kernels (rt_api.hip setup_slices: fp.slices = K, or -K for K
+    // on auto, decided here where the resident lanes are known: rt_slices.h brute_slice_launch): one-pass
+    // launches only, and no teams -- a set slice count keeps a tile the team rule would take on single lanes.
+    // The sliced kernels read FrameParams::slices as K | tail << 8 (a set slice count slices every pixel, auto
+    // only the tile's last pixels), 0 for an unsliced launch; the resumable walk reads fp.slices as it is
+    int bslices = 0;
+    if (brute && !listed && fp.pass == 0 && fp.team <= 1 && fp.slice_state && fp.slice_ready &&
+        sc.ntri + 2 < 65536 && fp.npix <= INT_MAX)
+        bslices = brute_slice_launch(fp.slices, fp.nloc, lanes);
+    if (!k.resume) f.slices = bslices;
+    // brute-force teams: a tile with fewer pixels than the device has lanes (a row slice of a multi-GPU frame)
+    // gives each pixel 4 lanes that split its box tests when it fills at most a quarter of them.  Measured on
+    // C2 tiles (one MI355X, 96-VGPR kernel: 327,680 resident lanes): a 1/8 tile (131k pixels) is fastest with
+    // single lanes (2.23 vs 2.29 ms with pairs), a 1/16 tile with teams of 4 (1.67 vs 1.88 with pairs, 2.28
+    // single).  (A listed add: the list's length is known on the device only -- one lane per pixel unless
+    // teams are set; the same for the walk's teams below.)
+    f.team = !brute ? 1 : bslices ? 1 : fp.team;
+    if (f.team == 0) f.team = (!listed && fp.nloc * 4 <= lanes) ? 4 : 1;
+    // team walk (render_resume_kernel TEAM): BVH2 item steps only; walk_team, 0 = auto (auto_walk_team;
+    // pass 2 of a pilot launch: the size pilot_team_pick_kernel chose, launch_render)
+    f.walk_team = 1;
+    if (k.resume && k.step && !k.wide && !k.log) {
+        f.walk_team = fp.walk_team ? fp.walk_team : listed ? 1 : auto_walk_team(fp.nloc, lanes);
+        if (f.walk_team != 2 && f.walk_team != 4 && f.walk_team != 8) f.walk_team = 1;
+    }
+    // the refill threshold of the one-lane brute-force kernels (fp.refill: the option; f.refill: R, or 0)
+    f.refill = (brute && f.team <= 1) ? brute_refill_launch(fp.refill, fp.nloc, lanes) : 0;
+    // teams, slices and the product kernels' refill threshold are instantiations of their own
+    k.ts = f.walk_team;
+    if (brute && f.team > 1) k.brute = 2;
+    else if (brute) k.brute |= (bslices ? kBruteSliced : 0) | (product && f.refill > 1 ? kBruteRefill : 0);
+    const void* fn = kernel_fn(k);
+    // the grid stays within what the device keeps resident (not that the slices' hand-off needs it: a job is only
+    // held by a running wave, and a pixel's slice k is taken before its slice k + 1)
+    const int64_t need = (fp.nloc * f.team * f.walk_team + block - 1) / block;
+    const int64_t grid = std::min(need, resident(fp.max_waves));
+    if (e != hipSuccess) return e;
+    // the samples-done words of the tile's pixels (the tree walk's are zeroed by setup_slices)
+    if (bslices) e = hipMemsetAsync(f.slice_ready, 0, (size_t)fp.nloc * sizeof(uint32_t), stream);
+    const LaunchConst* lc = nullptr;
+    if (e == hipSuccess) e = setup_work_block(f, d_work, stream, &lc);
+    if (e != hipSuccess) return e;
+    note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds});
+    DevScene a0 = sc;
+    void* args[] = {&a0, &f, &d_out, &d_counts, &d_work, &lc};
+    return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);
+}
+
+}  // namespace
+
+#ifndef RT_ACCUM_TU
+hipError_t launch_debug_log(const DevScene& sc, const FrameParams& fp, int traversal, float* d_out,
+                            unsigned int* d_work, hipStream_t stream) {
+    return launch_pick(sc, fp, choose_kernel(sc, fp, traversal, false, true, 0, 64), 64, d_out, nullptr, d_work, stream);
+}
+
 // ---- two-pass ordering (FrameParams::pass): pilot costs -> pixel order, most expensive first ----
 // Pixels are ordered in chunks of `chunk` consecutive tile pixels: the chunks by their summed pilot
 // cost, the pixels of a chunk in tile order.  The tree walk orders single pixels (its lanes diverge
@@ -1487,8 +1486,12 @@ __global__ void pilot_expand_kernel(const uint32_t* __restrict__ corder, int64_t
         order[q] = q < nfull * chunk ? corder[q / chunk] * (uint32_t)chunk + (uint32_t)(q % chunk) : (uint32_t)q;
 }
 
-hipError_t launch_render_pass(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
-                              unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream);
+// One pass of a one-shot frame: choose the engine, then launch_pick
+static hipError_t launch_pass(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
+                              unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
+    const KernelKey k = choose_kernel(sc, fp, traversal, d_counts != nullptr, false, 0, block);
+    return launch_pick(sc, fp, k, block, d_out, d_counts, d_work, stream);
+}
 
 // Two passes (fp.pilot > 0, product launches only): the first fp.pilot samples of every pixel,
 // then the rest of each pixel in descending order of the rays its (chunk's) pilot samples traced.  The
@@ -1497,10 +1500,10 @@ hipError_t launch_render_pass(const DevScene& sc, const FrameParams& fp, int tra
 hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
                          unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, RenderPending* pend) {
     if (fp.pilot <= 0 || fp.pass != 0 || d_counts || fp.spp <= fp.pilot || fp.nloc <= 0 || !fp.pilot_state)
-        return launch_render_pass(sc, fp, traversal, block, d_out, d_counts, d_work, stream);
+        return launch_pass(sc, fp, traversal, block, d_out, d_counts, d_work, stream);
     FrameParams a = fp;
     a.pass = 1;
-    hipError_t e = launch_render_pass(sc, a, traversal, block, d_out, nullptr, d_work, stream);
+    hipError_t e = launch_pass(sc, a, traversal, block, d_out, nullptr, d_work, stream);
     if (e != hipSuccess) return e;
     // scratch after the pixel order (rt_api.hip setup_pilot): bin totals | offs | chunk costs |
     // chunk order | segment histograms
@@ -1534,9 +1537,12 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
     b.pass = 2;
     // small tiles of the BVH2 walk: each pixel's remaining samples as speculative trails (rt_spec.hip):
     // a set number of trails, or (spec < 0) chosen on the device with the team size
-    const bool spec_ok = traversal == TRAV_FAST && fp.spec != 0 && fp.spec_log && fp.pilot_draws && spec_walk(sc, fp);
+    // (the walk rt_spec.hip continues is the BVH2 item-step resumable kernel, unstaged)
+    const KernelKey wk = choose_kernel(sc, fp, traversal, false, false, 0, block);
+    const bool spec_walk = wk.resume && wk.step && !wk.wide && !wk.smem;
+    const bool spec_ok = traversal == TRAV_FAST && fp.spec != 0 && fp.spec_log && fp.pilot_draws && spec_walk;
     if (spec_ok && fp.spec > 0) return launch_spec(sc, b, block, d_out, d_work, stream);
-    // (the brute-force kernels take their team size from the tile, launch_t: no pick, no read-back)
+    // (the brute-force kernels take their team size from the tile, launch_pick: no pick, no read-back)
     if (fp.walk_team == 0 && traversal == TRAV_FAST && sc.nbrute == 0) {
         // pass 2's team size from the pixels pass 1 left unfinished (pilot_team_pick_kernel)
         static_assert(kTeamOffset >= kGroups * kCounterStride && kTeamOffset + 8 <= kConstOffset, "work block layout");
@@ -1568,7 +1574,7 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
         if (pend) return hipSuccess;
         return launch_render_finish(sc, traversal, block, d_out, d_work, stream, P);
     }
-    return launch_render_pass(sc, b, traversal, block, d_out, nullptr, d_work, stream);
+    return launch_pass(sc, b, traversal, block, d_out, nullptr, d_work, stream);
 }
 
 hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, float* d_out, unsigned int* d_work,
@@ -1584,42 +1590,21 @@ hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, fl
         return launch_spec(sc, b, block, d_out, d_work, stream);
     }
     b.walk_team = pick;
-    return launch_render_pass(sc, b, traversal, block, d_out, nullptr, d_work, stream);
-}
-
-// the launches whose FAST walk is the BVH2 item-step resumable kernel (launch_fast's choice), the walk
-// rt_spec.hip continues
-bool spec_walk(const DevScene& sc, const FrameParams& fp) {
-    const bool smem = stage_in_lds(sc);
-    const bool resume = sc.ntri > 0 && sc.nbrute == 0 && fp.resume_min > 0;
-    const bool step = fp.step == 1 || (fp.step == 0 && (size_t)sc.nnodes * kNodeF4 * 16 <= kStepMaxBytes);
-    return resume && !smem && step && !(fp.wide && sc.wnodes);
-}
-
-hipError_t launch_render_pass(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
-                         unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
-    if (traversal == TRAV_REF) {
-        return d_counts ? launch_t<TRAV_REF, true, false>(sc, fp, block, d_out, d_counts, d_work, stream)
-                        : launch_t<TRAV_REF, false, false>(sc, fp, block, d_out, d_counts, d_work, stream);
-    }
-    return d_counts ? launch_fast<true>(sc, fp, block, d_out, d_counts, d_work, stream)
-                    : launch_fast<false>(sc, fp, block, d_out, d_counts, d_work, stream);
+    return launch_pass(sc, b, traversal, block, d_out, nullptr, d_work, stream);
 }
 
 #endif  // !RT_ACCUM_TU
 
 #if defined(RT_ACCUM_TU) && RT_ACCUM_TU == 1
-// One add of a progressive accumulation: the ACC instantiation of the one-pass kernel launch_render_pass picks
+// One add of a progressive accumulation: the ACC instantiation of the one-pass kernel launch_pass picks
 hipError_t launch_accum(const DevScene& sc, const FrameParams& f0, float4* state, int base, int traversal, int block,
                         float* d_out, unsigned int* d_work, hipStream_t stream) {
     if (!state || base < 0 || f0.spp <= base || f0.pass != 0 || f0.pilot != 0) return hipErrorInvalidValue;
     FrameParams fp = f0;
     fp.pilot_state = state;
     fp.pilot = base;
-    if (traversal == TRAV_REF)
-        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, kAccAdd>(sc, fp, block, d_out, nullptr,
-                                                                                             d_work, stream);
-    return launch_fast<false, kAccAdd>(sc, fp, block, d_out, nullptr, d_work, stream);
+    const KernelKey k = choose_kernel(sc, fp, traversal, false, false, kAccAdd, block);
+    return launch_pick(sc, fp, k, block, d_out, nullptr, d_work, stream);
 }
 
 #endif  // RT_ACCUM_TU == 1
@@ -1640,10 +1625,8 @@ hipError_t launch_accum_listed(const DevScene& sc, const FrameParams& f0, float4
     fp.slices = 0;
     fp.slice_state = nullptr;
     fp.slice_ready = nullptr;
-    if (traversal == TRAV_REF)
-        return launch_t<TRAV_REF, false, false, false, false, false, false, true, 0, kAccListed>(
-            sc, fp, block, d_out, nullptr, d_work, stream);
-    return launch_fast<false, kAccListed>(sc, fp, block, d_out, nullptr, d_work, stream);
+    const KernelKey k = choose_kernel(sc, fp, traversal, false, false, kAccListed, block);
+    return launch_pick(sc, fp, k, block, d_out, nullptr, d_work, stream);
 }
 
 // ---- adaptive sampling (rt_accum_mark / rt_accum_select*): which pixels a listed add refines ----

@@ -1,6 +1,6 @@
 // The host's rule for sample slices on brute-force scenes (option "slices"; the one-lane kernels of
 // rt_kernels.hip render_kernel).  Plain C++: rt_api.hip (setup_slices) makes the offer, rt_kernels.hip
-// (launch_t) decides where it knows its kernel's resident lanes, and rt_debug_brute_slices evaluates both
+// (launch_pick) decides where it knows its kernel's resident lanes, and rt_debug_brute_slices evaluates both
 // for tests/test_brute_slices_rule.py.  Frames do not depend on any of it; the frame time does.
 #pragma once
 #include <algorithm>
@@ -40,7 +40,7 @@ inline int brute_slice_tail(int64_t nloc, int64_t lanes) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(256, (2 * 256 * lanes + nloc - 1) / std::max<int64_t>(nloc, 1)));
 }
 
-// What launch_t makes of the offer on a tile of nloc pixels with `lanes` resident lanes: FrameParams::slices as
+// What launch_pick makes of the offer on a tile of nloc pixels with `lanes` resident lanes: FrameParams::slices as
 // the sliced kernels read it, K | tail << 8 (a set slice count slices every pixel: tail 256), or 0 for an
 // unsliced launch
 inline int brute_slice_launch(int offer, int64_t nloc, int64_t lanes) {

@@ -22,9 +22,6 @@
 // records or at a sample that draws nothing (fixed_point: every later sample repeats it).
 // So the frame is the serial one bit for bit whatever the guesses; only the work and the chain's
 // latency depend on them (tools/chain_speculation.py prices both on the CPU oracle).
-#include <mutex>
-#include <vector>
-
 #include "rt_device.h"
 
 namespace rt {
@@ -454,46 +451,23 @@ hipError_t launch_spec(const DevScene& sc, const FrameParams& fp, int block, flo
     const void* fn = fp.spec == 2   ? (ovf ? spec_fn<true, 2>() : spec_fn<false, 2>())
                      : fp.spec == 4 ? (ovf ? spec_fn<true, 4>() : spec_fn<false, 4>())
                                     : (ovf ? spec_fn<true, 8>() : spec_fn<false, 8>());
-    const size_t lds = (size_t)2 * std::max(sc.stack_lds, 1) * (size_t)block * sizeof(int);
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    {
-        // blocks per CU of each (instantiation, block, LDS), queried once per device (a context may hold
-        // devices of different kinds): the host query costs more than the launch
-        struct Occ { int dev; const void* fn; int block; size_t lds; int per_cu; };
-        static std::mutex mu;
-        static std::vector<Occ> seen;
-        std::lock_guard<std::mutex> g(mu);
-        for (const Occ& o : seen)
-            if (o.dev == dev && o.fn == fn && o.block == block && o.lds == lds) per_cu = o.per_cu;
-        if (per_cu == 0) {
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, lds);
-            if (e != hipSuccess) return e;
-            seen.push_back({dev, fn, block, lds, per_cu});
-        }
-    }
-    const int cap_cu = fp.max_waves > 0 ? std::max(1, fp.max_waves * 4 * 64 / block) : INT_MAX;
+    const size_t lds = stack_lds_bytes(sc, TRAV_FAST, block);
+    hipError_t e = hipSuccess;
     // at most kWalkLanesPerCu lanes per CU: one trail log each (spec_log_bytes)
-    const int cap_logs = std::max(1, kWalkLanesPerCu / block);
-    const int64_t resident = (int64_t)std::max(1, cus) * std::max(1, std::min({per_cu, cap_cu, cap_logs}));
-    const int64_t grid = std::min<int64_t>((fp.nloc * fp.spec + block - 1) / block, resident);
-    // the work block's counters and launch constants were set up by pass 1's launch (launch_t): pass 2
-    // re-zeroes the counters and recomputes the constants the same way
-    e = hipMemsetAsync(d_work, 0, (size_t)kGroups * kCounterStride, stream);
+    constexpr int cap_logs = kWalkLanesPerCu / (4 * 64);   // as waves per SIMD
+    const int max_waves = fp.max_waves > 0 ? std::min(fp.max_waves, cap_logs) : cap_logs;
+    const int64_t resident = resident_blocks(fn, block, lds, max_waves, &e);
     if (e != hipSuccess) return e;
-    LaunchConst* lc = reinterpret_cast<LaunchConst*>(reinterpret_cast<char*>(d_work) + kConstOffset);
-    hipLaunchKernelGGL(make_const_kernel, dim3(1), dim3(64), 0, stream, fp, lc);
+    const int64_t grid = std::min<int64_t>((fp.nloc * fp.spec + block - 1) / block, resident);
+    // the work block's counters and launch constants were set up by pass 1's launch: pass 2 re-zeroes the
+    // counters and recomputes the constants the same way
+    const LaunchConst* lc = nullptr;
+    e = setup_work_block(fp, d_work, stream, &lc);
+    if (e != hipSuccess) return e;
     DevScene a0 = sc;
     FrameParams a1 = fp;
-    float* a2 = d_out;
-    unsigned int* a3 = d_work;
-    const LaunchConst* a4 = lc;
-    void* args[] = {&a0, &a1, &a2, &a3, &a4};
-    e = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    void* args[] = {&a0, &a1, &d_out, &d_work, &lc};
+    return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);
 }
 
 }  // namespace rt

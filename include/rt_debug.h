@@ -118,6 +118,15 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
  * tree walk, K | share << 8 (as above) for a sliced brute-force launch. */
 int rt_debug_last_slices(void);
 
+/* The process's last render launch, as its kernel got it.  out[0..10] = the kernel's key: traversal (0 FAST,
+ * 1 REF), count (instrumented), log, smem (scene staged in LDS), ovf (stack overflow buffer), resume (the
+ * resumable tree walk), step (1 item steps, 0 rounds), wide (0 BVH2, 1 the 4-wide layout, 2 with origin-folded
+ * dequantisation), brute (0 none, 1 lock-step, 2 teams, 3 clustered, + 4 sample slices, + 8 refill threshold),
+ * ts (lanes per pixel of the tree walk), acc (0 one-shot, 1 an add, 2 a listed add); out[11..14] = the brute-force
+ * team size, the walk's team size, the slice word (rt_debug_last_slices) and R (rt_debug_last_refill) of its
+ * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block. */
+int rt_debug_last_launch(int32_t out[17]);
+
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
  * lanes of the kernel resident.  *out = R, the free lanes a wave waits for before it hands out jobs, or 0 when

@@ -1,5 +1,5 @@
 """The host's rule for the refill threshold of the one-lane brute-force kernels (csrc/rt_internal.h
-brute_refill_launch, through rt_debug_brute_refill): the R that launch_t gives its kernel for option
+brute_refill_launch, through rt_debug_brute_refill): the R that launch_pick gives its kernel for option
 "brute_refill".  Frames are bit-identical whatever R is (tests/test_gpu_brute_refill.py), so only this file
 notices a rule that turns the headline's threshold off, or one that turns it on for the small tiles."""
 import pytest

@@ -1,5 +1,5 @@
 """The host's rule for sample slices on brute-force scenes (csrc/rt_slices.h, through rt_debug_brute_slices): what
-setup_slices offers a launch and what launch_t makes of it, on the host alone.  Frames are bit-identical whether
+setup_slices offers a launch and what launch_pick makes of it, on the host alone.  Frames are bit-identical whether
 or not slices are taken and whatever share of the pixels is sliced, so only this file notices a rule that turns
 the headline's slices off, or one that slices every pixel of the frame."""
 import pytest

@@ -2,7 +2,7 @@
 renders the frame of the lock-step loop, bit for bit.  -1 (auto) and 1 (force) against 0 (off).  The clustered
 loop is the one-lane kernel's, and tiles this small would run teams of 4 by default, so every comparison runs
 with team = 1 as well as with the default team size.  Auto keeps tiles of less than a pixel per resident lane on
-the lock-step kernel (rt_kernels.hip launch_t), so on these frames it is force that runs the clustered kernel;
+the lock-step kernel (rt_kernels.hip launch_pick), so on these frames it is force that runs the clustered kernel;
 auto must still give the same bits."""
 import numpy as np
 import pytest

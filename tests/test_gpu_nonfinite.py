@@ -243,7 +243,7 @@ def count(kl, sc, traversal="fast", **options):
 def other_fast_paths(sc):
     """The FAST paths that must agree bit for bit with the default one.  The larger scene here is soup150:
     16.7 KB of nodes and triangles at depth 10 (wide depth 14), which the default 20-entry LDS stack lets
-    launch_fast stage in LDS (the SMEM kernels, BVH2 only -- bvh_width 4 alone would be that same kernel, so
+    choose_kernel stage in LDS (the SMEM kernels, BVH2 only -- bvh_width 4 alone would be that same kernel, so
     it is not listed).  stack_lds 8 is below its depth: the scene then walks global memory with the overflow
     buffer, the kernels of larger scenes, and only then does bvh_width 4 reach the 4-wide walk."""
     if _ntri(sc) <= 64:
@@ -517,7 +517,7 @@ def test_schedules_render_the_zero_normal_scene_identically(kl):
 
 
 def test_wide_walk_camera_check_with_nan_components(kl):
-    """launch_fast picks the origin-folded dequantisation of the 4-wide walk when every camera coordinate is
+    """choose_kernel picks the origin-folded dequantisation of the 4-wide walk when every camera coordinate is
     within DevScene::wdq_omax.  The check must be false for a NaN coordinate in any position (std::max drops
     a NaN second operand, so a maximum over the three would keep only a NaN in cam[0]).  soup2000 is too large
     to stage in LDS, so bvh_width 4 is the 4-wide walk; with wdq on and off the frame is the oracle's."""

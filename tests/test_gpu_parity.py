@@ -1081,7 +1081,7 @@ def test_wide_origin_folded_dequantisation_renders_identically(kl, case):
     rounds differently; the builder keeps every bound with q > 0 at least 2^-17 P outside its exact
     bound, which covers both roundings for ray origins up to scene_info's wdq_omax (rt_api.hip
     emit_wide), so the accepted triangles -- and the frame -- are the exact form's and the oracle's.  A
-    camera beyond the bound renders with the exact form (launch_fast), the same frame again."""
+    camera beyond the bound renders with the exact form (choose_kernel), the same frame again."""
     if case == "grid":
         sc, cam, env, npix, spp, mb, ibl = W.CONFIGS["C5"].with_size(48, 27, 2).inputs()
     else:

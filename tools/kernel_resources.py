@@ -56,6 +56,7 @@ def main():
         co = code_object(obj, td)
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
     cur = {}
+    ahead = {}
     rows = []
     for line in notes.splitlines():
         m = re.match(r"\s*\.(name|private_segment_fixed_size|vgpr_count|sgpr_count|group_segment_fixed_size|"
@@ -66,7 +67,10 @@ def main():
         if k == "name" and not v.endswith(".kd"):
             if cur.get("name"):
                 rows.append(cur)
-            cur = {"name": v}
+            cur = dict(ahead, name=v)
+            ahead = {}
+        elif k in ("agpr_count", "group_segment_fixed_size"):   # a kernel's keys are sorted: these precede its name
+            ahead[k] = v
         elif cur:
             cur[k] = v
     if cur.get("name"):
@@ -74,7 +78,7 @@ def main():
     for r in rows:
         if filt in r["name"]:
             print(f"vgpr {r.get('vgpr_count', '?'):>4} agpr {r.get('agpr_count', '?'):>3} sgpr {r.get('sgpr_count', '?'):>4} "
-                  f"scratch {r.get('private_segment_fixed_size', '?'):>5} spill v/s {r.get('vgpr_spill_count', '?')}/"
+                  f"lds {r.get('group_segment_fixed_size', '?'):>5} scratch {r.get('private_segment_fixed_size', '?'):>5} spill v/s {r.get('vgpr_spill_count', '?')}/"
                   f"{r.get('sgpr_spill_count', '?')}  {r['name']}")
 
 
