@@ -157,6 +157,36 @@ class Progressive(object):
             n = self.select(threshold)
         return out
 
+    # -- denoised previews: presentable frames from the first few samples.  Nothing is rendered and the
+    # accumulation is untouched: ``image()`` stays the exact frame. --
+    def guides(self) -> dict:
+        """The first-hit guide buffers (rt_accum_guides), as views of one ``[imgDim, 12]`` array: ``normal``
+        ``[n, 3]`` and ``depth`` ``[n]`` (0, 0, 0 and -1 on a miss), ``position`` ``[n, 3]``, ``albedo`` ``[n, 3]``
+        (1, 1, 1 where the pixel is not filterable), ``material`` int32 ``[n]`` (-1 on a miss) and
+        ``filterable_samples`` int32 ``[n]``: the pixel's sample count where its first hit is diffuse or glossy,
+        else 0."""
+        self._live()
+        g = self._ctx.accum_guides()
+        return {"normal": g[:, 0:3], "depth": g[:, 3], "position": g[:, 4:7], "albedo": g[:, 8:11],
+                "material": g[:, 11].view(np.int32), "filterable_samples": g[:, 7].view(np.int32)}
+
+    def denoised(self, passes: int = 5, normal_squarings: int = 5, sigma_c: float = 1.5, sigma_p: float = 0.02,
+                 out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The frame at the samples done, through the edge-aware filter of rt_api.h (rt_accum_denoise): a
+        preview for display.  Pixels whose first hit is not diffuse or glossy are ``image()``'s, bit for bit."""
+        passes, normal_squarings = int(passes), int(normal_squarings)
+        sigma_c, sigma_p = float(sigma_c), float(sigma_p)
+        if not 1 <= passes <= 8:
+            raise ValueError("passes must be 1..8")
+        if not 0 <= normal_squarings <= 8:
+            raise ValueError("normal_squarings must be 0..8")
+        for name, v in (("sigma_c", sigma_c), ("sigma_p", sigma_p)):
+            if not (v > 0.0 and v != float("inf")):
+                raise ValueError(f"{name} must be finite and > 0")
+        out = self._out(out, np.float32)
+        self._ctx.accum_denoise(_native.DenoiseParams(passes, normal_squarings, sigma_c, sigma_p), out=out.reshape(-1))
+        return out
+
     @property
     def samples(self) -> int:
         """Samples done per pixel -- the most a pixel holds once ``add_selected`` made them differ (-1 once closed)."""

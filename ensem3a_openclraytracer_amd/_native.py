@@ -35,6 +35,7 @@ EXPORTED = (
     "rt_accum_mark", "rt_accum_select", "rt_accum_select_mask", "rt_accum_select_all", "rt_accum_selection",
     "rt_accum_sample_map", "rt_accum_add_selected", "rt_accum_mark_device", "rt_accum_select_device",
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
+    "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
@@ -51,6 +52,18 @@ HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_o
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
+
+
+class DenoiseParams(ctypes.Structure):
+    """rt_denoise_params of rt_api.h; the defaults are the library's."""
+    _fields_ = [("passes", ctypes.c_int), ("normal_squarings", ctypes.c_int),
+                ("sigma_c", ctypes.c_float), ("sigma_p", ctypes.c_float)]
+
+    def __init__(self, passes: int = 5, normal_squarings: int = 5, sigma_c: float = 1.5, sigma_p: float = 0.02):
+        super().__init__(int(passes), int(normal_squarings), float(sigma_c), float(sigma_p))
+
+
+GUIDE_FLOATS = 12   # three float4 per pixel: n | k, P | f, a | m (rt_api.h)
 
 
 class NativeError(RuntimeError):
@@ -132,6 +145,10 @@ def lib():
             "rt_accum_select_mask_device": (_i32, [_c_p, _i32, _c_p, _c_p]),
             "rt_accum_select_all_device": (_i32, [_c_p, _i32, _c_p]),
             "rt_accum_add_selected_device": (_i32, [_c_p, _i32, _i32, _c_p, _c_p]),
+            "rt_accum_guides": (_i32, [_c_p, _c_p]),
+            "rt_accum_guides_device": (_i32, [_c_p, _i32, _c_p, _c_p]),
+            "rt_denoise_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, ctypes.POINTER(DenoiseParams), _c_p, _c_p]),
+            "rt_accum_denoise": (_i32, [_c_p, ctypes.POINTER(DenoiseParams), _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -437,6 +454,35 @@ class Context:
     def accum_add_selected_device(self, spp: int, d_out_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
         self._check(lib().rt_accum_add_selected_device(self.handle, int(device_index), int(spp), _c_p(int(d_out_ptr)),
                                                        self._stream(stream_ptr)))
+
+    # -- denoised previews (rt_accum_guides* / rt_denoise_device / rt_accum_denoise) --
+    def accum_guides(self) -> np.ndarray:
+        """The guide buffers of the open accumulation, float32[npix, 12]: n | k, P | f, a | m (f, m: int bits)."""
+        n = getattr(self, "_accum_npix", 0)
+        out = np.zeros((max(n, 1), GUIDE_FLOATS), np.float32)
+        self._check(lib().rt_accum_guides(self.handle, out.ctypes.data))
+        return out[:n]
+
+    def accum_guides_device(self, d_guides_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
+        self._check(lib().rt_accum_guides_device(self.handle, int(device_index),
+                                                 _c_p(int(d_guides_ptr)) if d_guides_ptr else None,
+                                                 self._stream(stream_ptr)))
+
+    def denoise_device(self, d_rgb_ptr: int, d_guides_ptr: int, npix: int, width: int, d_out_ptr: int,
+                       params: "DenoiseParams" = None, stream_ptr: int = 0, device_index: int = 0) -> None:
+        """rt_denoise_device: filter a frame in device memory (``params`` None = the defaults)."""
+        self._check(lib().rt_denoise_device(self.handle, int(device_index),
+                                            _c_p(int(d_rgb_ptr)) if d_rgb_ptr else None,
+                                            _c_p(int(d_guides_ptr)) if d_guides_ptr else None, int(npix), int(width),
+                                            ctypes.byref(params) if params is not None else None,
+                                            _c_p(int(d_out_ptr)) if d_out_ptr else None, self._stream(stream_ptr)))
+
+    def accum_denoise(self, params: "DenoiseParams" = None, out: np.ndarray = None) -> np.ndarray:
+        """The open accumulation's frame, denoised (float32[3*npix]); the state is untouched."""
+        out = self._accum_out(out, np.float32)
+        self._check(lib().rt_accum_denoise(self.handle, ctypes.byref(params) if params is not None else None,
+                                           out.ctypes.data))
+        return out
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

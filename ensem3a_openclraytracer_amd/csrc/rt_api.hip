@@ -32,6 +32,10 @@
 // lanes still rendering: 36 on the BVH2 walk (C3 / C4 ms at 32 / 36 / 40: 138.8 / 136.8 / 136.5,
 // 446.8 / 452.6 / 455.0), 48 on the 4-wide walk (C5 at 40 / 48 / 52: 5,805 / 5,705 / 5,772)
 constexpr int kResumeMinBvh2 = 36, kResumeMinWide = 48;
+// Denoise filter: the pass at step 1 stages its tile in LDS (rt_set_option "denoise_lds"; -1 = auto); every
+// other pass reads its taps from global memory.  5 passes, ms: C2's frame 0.394 -> 0.371, C4's 0.298 -> 0.293;
+// the pass at step 2 tiled the same way is slower than its taps from global memory
+constexpr int kDenoiseLds = 1;
 
 using rt::HostScene;
 
@@ -71,6 +75,10 @@ struct Device {
     bool sel_all = false;         // the selection is rt_accum_select_all's
     int64_t sel_known = -1;       // the selection's length where the host knows it (the host forms), else -1
     int64_t acc_full = 0;
+    // Denoised previews (rt_accum_guides*, rt_denoise_device, rt_accum_denoise), each allocated on first use: the
+    // filter's scratch (X twice, N, P: 64 bytes per frame pixel) and the launch constants of the guide kernel;
+    // the host forms' guides of this slot's tile; and, on the slot that filters, the frame-shaped input and output
+    DevBuf dn, dn_const, guides, dn_rgb, dn_guides, dn_out;
     char* host_stage = nullptr;   // pinned staging for rt_render / rt_render_rgb8
     int* host_pick = nullptr;     // pinned: a two-pass launch's pass-2 pick, read back (rt::RenderPending)
     size_t host_stage_bytes = 0;
@@ -116,6 +124,7 @@ struct rt_ctx {
     int handout = -1;     // pixel hand-out: 0 = interleaved chunks, 1 = a contiguous block per XCD group, -1 = auto
     int slices = -1;      // one-pass tree-walk launches: sample slices per pixel (FrameParams::slices; 0 off, -1 auto)
     int brute_refill = -1;   // one-lane brute-force kernels: free lanes a wave refills together (FrameParams::refill; -1 auto, 0 or 1 off, R)
+    int denoise_lds = -1;    // the filter's pass at step 1 stages its tile in LDS (0 off, 1 on, -1 auto: kDenoiseLds)
     bool accum_host = false;   // the open accumulation is rt_accum_begin's: every slot holds its rows of one frame
     // host wall times of the last calls (rt_debug_timings), ms: rt_set_scene's validation + packing and its
     // uploads (+ the per-triangle frame kernel), rt_set_env (upload + texel-sum kernel), rt_render's
@@ -367,7 +376,8 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.pending) (void)hipEventSynchronize(d.done);
         if (d.stream) (void)hipStreamSynchronize(d.stream);
         for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.brute_cbox, &d.brute_crow, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
-                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum, &d.mark, &d.sel, &d.all})
+                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum, &d.mark, &d.sel, &d.all,
+                          &d.dn, &d.dn_const, &d.guides, &d.dn_rgb, &d.dn_guides, &d.dn_out})
             release(*b);
         if (d.host_stage) (void)hipHostFree(d.host_stage);
         if (d.host_pick) (void)hipHostFree(d.host_pick);
@@ -513,6 +523,11 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         if (value < -1 || value > rt::kRefillMax)
             return set_err(ctx, RT_ERR_ARG, "brute_refill must be -1 (auto), 0 or 1 (off) or 2..%d", rt::kRefillMax);
         ctx->brute_refill = (int)value;
+        return RT_OK;
+    }
+    if (!std::strcmp(key, "denoise_lds")) {
+        if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "denoise_lds must be -1 (auto), 0 or 1");
+        ctx->denoise_lds = (int)value;
         return RT_OK;
     }
     if (!std::strcmp(key, "wdq")) {
@@ -1432,6 +1447,148 @@ int rt_accum_sample_map(rt_ctx* ctx, int32_t* out) {
 
 int rt_accum_add_selected(rt_ctx* ctx, int spp, float* out_rgb) {
     return accum_host(ctx, spp, false, out_rgb, -1, "rt_accum_add_selected", true);
+}
+
+// ---- denoised previews: the guide buffers of the state, the filter ----
+namespace {
+int denoise_params(rt_ctx* ctx, const rt_denoise_params* in, rt_denoise_params* out) {
+    const rt_denoise_params defaults = {5, 5, 1.5f, 0.02f};
+    *out = in ? *in : defaults;
+    if (out->passes < 1 || out->passes > 8)
+        return set_err(ctx, RT_ERR_ARG, "denoise: passes must be 1..8, got %d", out->passes);
+    if (out->normal_squarings < 0 || out->normal_squarings > 8)
+        return set_err(ctx, RT_ERR_ARG, "denoise: normal_squarings must be 0..8, got %d", out->normal_squarings);
+    if (!(std::isfinite(out->sigma_c) && out->sigma_c > 0.0f) || !(std::isfinite(out->sigma_p) && out->sigma_p > 0.0f))
+        return set_err(ctx, RT_ERR_ARG, "denoise: sigma_c and sigma_p must be finite and > 0, got %g, %g",
+                       (double)out->sigma_c, (double)out->sigma_p);
+    return RT_OK;
+}
+
+// the open host accumulation, every slot usable and holding samples (the checks of rt_accum_read)
+int accum_host_readable(rt_ctx* ctx, const char* what) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
+    for (int k = 0; k < (int)ctx->devs.size(); ++k) {
+        Device* dp = nullptr;
+        const int st = accum_slot_of(ctx, k, what, &dp);
+        if (st) return st;
+    }
+    return RT_OK;
+}
+}  // namespace
+
+int rt_accum_guides_device(rt_ctx* ctx, int device_index, float* d_guides, void* stream) {
+    Device* dp = nullptr;
+    int st = accum_slot_of(ctx, device_index, "rt_accum_guides", &dp);
+    if (st) return st;
+    Device& d = *dp;
+    if (!d_guides) return set_err(ctx, RT_ERR_ARG, "rt_accum_guides: the output must not be NULL");
+    if ((uintptr_t)d_guides & 15) return set_err(ctx, RT_ERR_ARG, "rt_accum_guides: d_guides must be 16-byte aligned");
+    rt::FrameParams fp;
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, 0, d.acc_row0, d.acc_row_step, &fp);
+    if (st) return st;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, accum_ensure(d, d.dn_const, rt::launch_const_bytes()));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_accum_guides(dev_scene(ctx, d), fp, (const float4*)d.accum.p, d.dn_const.p,
+                                            (float4*)d_guides, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int rt_accum_guides(rt_ctx* ctx, float* out) {
+    int st = accum_host_readable(ctx, "rt_accum_guides");
+    if (st) return st;
+    if (!out) return set_err(ctx, RT_ERR_ARG, "rt_accum_guides: the output must not be NULL");
+    for (int k = 0; k < (int)ctx->devs.size(); ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, accum_ensure(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
+        st = rt_accum_guides_device(ctx, k, (float*)d.guides.p, d.stream);
+        if (st) return st;
+    }
+    return accum_gather_host(ctx, out, 12 * sizeof(float), [](Device& d) { return (const void*)d.guides.p; });
+}
+
+int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const float* d_guides, int64_t npix, int width,
+                      const rt_denoise_params* params, float* d_out, void* stream) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    rt_denoise_params P;
+    const int st = denoise_params(ctx, params, &P);
+    if (st) return st;
+    if (!d_rgb || !d_guides || !d_out) return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: NULL buffer");
+    if ((uintptr_t)d_guides & 15) return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: d_guides must be 16-byte aligned");
+    if (npix < 1 || npix > 0x7fffffff || width < 1)
+        return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: bad frame (%lld pixels, rows of %d)", (long long)npix, width);
+    Device& d = ctx->devs[device_index];
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, accum_ensure(d, d.dn, rt::denoise_scratch_bytes(npix)));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_denoise(d_rgb, (const float4*)d_guides, npix, width, P.passes, P.normal_squarings,
+                                       P.sigma_c, P.sigma_p, (ctx->denoise_lds >= 0 ? ctx->denoise_lds : kDenoiseLds) != 0,
+                                       (float4*)d.dn.p, d_out, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb) {
+    int st = accum_host_readable(ctx, "rt_accum_denoise");
+    if (st) return st;
+    if (!out_rgb) return set_err(ctx, RT_ERR_ARG, "rt_accum_denoise: the output must not be NULL");
+    rt_denoise_params P;
+    st = denoise_params(ctx, params, &P);
+    if (st) return st;
+    const int nd = (int)ctx->devs.size();
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    // every slot resolves the frame and the guides of its rows
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, accum_ensure(d, d.out, (size_t)d.acc_nloc * 3 * sizeof(float)));
+        HIP_OR_RET(ctx, accum_ensure(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
+        if (d.acc_nloc > 0) {
+            HIP_OR_RET(ctx, order_after_last(d, d.stream));
+            HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, (float*)d.out.p, d.acc_nloc, d.stream));
+            HIP_OR_RET(ctx, mark_launch(d, d.stream));
+        }
+        st = rt_accum_guides_device(ctx, k, (float*)d.guides.p, d.stream);
+        if (st) return st;
+    }
+    Device& d0 = ctx->devs[0];
+    const float* rgb = (const float*)d0.out.p;   // one slot: its tile is the frame, everything stays on the device
+    const float* guides = (const float*)d0.guides.p;
+    std::vector<float> h_rgb, h_guides;          // (kept until the uploads are done)
+    if (nd > 1) {   // several slots: the rows assembled into frame-shaped buffers on slot 0, through the host
+        h_rgb.resize((size_t)npix * 3);
+        h_guides.resize((size_t)npix * 12);
+        st = accum_gather_host(ctx, h_rgb.data(), 3 * sizeof(float), [](Device& d) { return (const void*)d.out.p; });
+        if (st) return st;
+        st = accum_gather_host(ctx, h_guides.data(), 12 * sizeof(float), [](Device& d) { return (const void*)d.guides.p; });
+        if (st) return st;
+        HIP_OR_RET(ctx, hipSetDevice(d0.id));
+        HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_rgb, h_rgb.size() * sizeof(float)));
+        HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_guides, h_guides.size() * sizeof(float)));
+        HIP_OR_RET(ctx, order_after_last(d0, d0.stream));
+        HIP_OR_RET(ctx, hipMemcpyAsync(d0.dn_rgb.p, h_rgb.data(), h_rgb.size() * sizeof(float), hipMemcpyHostToDevice, d0.stream));
+        HIP_OR_RET(ctx, hipMemcpyAsync(d0.dn_guides.p, h_guides.data(), h_guides.size() * sizeof(float), hipMemcpyHostToDevice,
+                                       d0.stream));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d0.stream));
+        rgb = (const float*)d0.dn_rgb.p;
+        guides = (const float*)d0.dn_guides.p;
+    }
+    HIP_OR_RET(ctx, hipSetDevice(d0.id));
+    HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_out, (size_t)npix * 3 * sizeof(float)));
+    st = rt_denoise_device(ctx, 0, rgb, guides, npix, W, &P, (float*)d0.dn_out.p, d0.stream);
+    if (st) return st;
+    HIP_OR_RET(ctx, hipMemcpyAsync(out_rgb, d0.dn_out.p, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, d0.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d0.stream));
+    return RT_OK;
 }
 
 int rt_render(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,

@@ -224,6 +224,20 @@ hipError_t launch_select_compact(const uint8_t* flag, int64_t n, uint32_t* scrat
                                  hipStream_t stream);
 hipError_t launch_list_all(uint32_t* list, int64_t n, uint32_t* count, hipStream_t stream);
 hipError_t launch_sample_map(const float4* state, int32_t* out, int64_t n, hipStream_t stream);
+// Denoised previews (rt_accum_guides*, rt_denoise_device; kernels in rt_denoise.hip's translation unit):
+//   launch_accum_guides  d_guides[3 p ..] = the three guide float4 (rt_api.h) of the fp.nloc tile pixels of a
+//                        state; fp carries the camera and the tile (check_frame), lconst is device scratch of
+//                        launch_const_bytes() that the launch fills with the frame's launch constants;
+//   launch_denoise       the filter of rt_api.h over a frame of npix pixels, rows of `width`: d_rgb, d_guides ->
+//                        d_out (which may not overlap them); scratch: denoise_scratch_bytes(npix), 16-byte aligned;
+//                        lds: the pass at step 1 stages its tile in LDS (the same bits).
+size_t launch_const_bytes();
+hipError_t launch_accum_guides(const DevScene& sc, const FrameParams& fp, const float4* state, void* lconst,
+                               float4* d_guides, hipStream_t stream);
+size_t denoise_scratch_bytes(int64_t npix);
+hipError_t launch_denoise(const float* d_rgb, const float4* d_guides, int64_t npix, int width, int passes, int nsq,
+                          float sigma_c, float sigma_p, bool lds, float4* scratch, float* d_out,
+                          hipStream_t stream);
 // out[3 p ..] = clamp(acc / s) of the n pixels of an accumulation state (rt_accum_read)
 hipError_t launch_accum_resolve(const float4* state, float* d_out, int64_t n, hipStream_t stream);
 hipError_t launch_prep_frames(const DevScene& sc, float4* frame, hipStream_t stream);

@@ -208,6 +208,66 @@ int rt_accum_select_mask_device(rt_ctx* ctx, int device_index, const uint8_t* d_
 int rt_accum_select_all_device(rt_ctx* ctx, int device_index, void* stream);
 int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream);
 
+/* Denoised previews: first-hit guide buffers out of the accumulation's state, and an edge-aware filter they
+ * drive.  Nothing is rendered, no ray is traced and the state is untouched: rt_accum_read before and after
+ * gives the same bits.
+ *
+ * Guides: three float4 per pixel (12 floats), from the pixel's cached camera hit and its own sample count.
+ *   G0 = (n.x, n.y, n.z, k)   n the normal the shading uses (the first vertex's, face[4]), k the hit distance;
+ *                             a miss gives (0, 0, 0, -1);
+ *   G1 = (P.x, P.y, P.z, f)   P = o + d * k per component (one multiply, then one add) on the pixel's camera ray,
+ *                             0 on a miss; f (int bits) = the pixel's sample count where it is filterable, else 0;
+ *   G2 = (a.r, a.g, a.b, m)   m (int bits) the material index, -1 on a miss; a = max(colour, 0.01f) per channel
+ *                             of a filterable pixel, else (1, 1, 1).
+ * A pixel is filterable when its first hit's material is of type 1 (diffuse) or 2 (glossy).  Misses and emitters
+ * draw no random number and carry no noise; a glass first hit shows geometry the guides do not describe.
+ * Apart from f the guides do not depend on the samples added.
+ *   rt_accum_guides         host form, out[12 * npix] in frame order;
+ *   rt_accum_guides_device  slot device_index's tile into DEVICE memory d_guides, packed as d_out of
+ *                           rt_accum_add_device is (12 floats per tile pixel, 16-byte aligned); padding pixels of
+ *                           a partial last row get the miss pattern (f = 0, m = -1).  Enqueues on `stream`
+ *                           and never waits.
+ * RT_ERR_STATE with no accumulation open, before the first add, or after an invalidation; RT_ERR_ARG for a NULL
+ * output.
+ *
+ * The filter (rt_denoise_device) is a whole-frame image operation on one device, independent of the accumulation:
+ * d_rgb[3 * npix] and d_guides[12 * npix] in frame order (rows of `width`, H = ceil(npix / width) rows) give
+ * d_out[3 * npix], which may not overlap them.  A NULL params means the defaults.  Definition -- everything is
+ * fp32, evaluated in the order written, without contraction:
+ *   1. Demodulate: a filterable pixel (f > 0) has x = c / a per channel.  Any other pixel is not filtered: its
+ *      output is its input, copied bit for bit.
+ *   2. Pass i = 0 .. passes - 1, step = 1 << i, for each filterable pixel p: acc = 0, ws = 0; taps dy = -2 .. 2
+ *      (outer), dx = -2 .. 2 (inner), q = p + (dx, dy) * step, h = K[|dx|] * K[|dy|], K = {3/8, 1/4, 1/16}.
+ *      The centre tap has w = h (9/64).  A tap outside [0, width) x [0, H), one whose pixel index is >= npix,
+ *      and a tap on a pixel that is not filterable have w = 0.  Otherwise
+ *          t   = max(0, (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z)
+ *          wn  = t, squared normal_squarings times
+ *          d   = P_q - P_p;  dpl = |(n_p.x * d.x + n_p.y * d.y) + n_p.z * d.z|
+ *          a_  = dpl / (sigma_p * k_p);  wp = 1 / (1 + a_ * a_)
+ *          dc  = x_q - x_p (this pass's input);  d2 = (dc.r * dc.r + dc.g * dc.g) + dc.b * dc.b
+ *          sc2 = ((sigma_c * sigma_c) / (float)s_p) / (float)(step * step);  wc = 1 / (1 + d2 / sc2)
+ *          w   = (h * (wn * wp)) * wc
+ *      then acc += w * x_q per channel (multiply, then add) and ws += w; after the taps x'_p = acc / ws
+ *      (ws >= 9/64).  A pass reads only the previous pass's output.
+ *   3. Remodulate: out = max(min(x * a, 1), 0).
+ * The colour bandwidth narrows with 1 / sqrt(s_p) as Monte-Carlo noise does, so it follows each pixel's own count.
+ * rt_denoise_device enqueues on `stream` and waits only when its scratch buffers (64 bytes per pixel, the device
+ * slot's, allocated on first use) have to grow.  RT_ERR_ARG: NULL buffers, npix < 1, width < 1, passes outside
+ * 1..8, normal_squarings outside 0..8, a sigma that is not finite and > 0.
+ *   rt_accum_denoise  host form: resolves the frame and the guides on every slot, filters the whole frame on slot
+ *                     0 (with several slots the rows are assembled there through the host) and reads
+ *                     out_rgb[3 * npix] back, blocking.  Errors as rt_accum_read, and RT_ERR_ARG as above. */
+typedef struct {
+    int passes;              /* 1..8, default 5: step 1, 2, 4, ... */
+    int normal_squarings;    /* 0..8, default 5 */
+    float sigma_c, sigma_p;  /* > 0, finite; defaults 1.5f, 0.02f */
+} rt_denoise_params;
+int rt_accum_guides(rt_ctx* ctx, float* out);
+int rt_accum_guides_device(rt_ctx* ctx, int device_index, float* d_guides, void* stream);
+int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const float* d_guides, int64_t npix,
+                      int width, const rt_denoise_params* params, float* d_out, void* stream);
+int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),

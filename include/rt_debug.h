@@ -26,7 +26,9 @@
  *   "wdq"          4-wide walk: origin-folded dequantisation where the builder's gap covers the camera (1)
  *   "waves"        persistent grid: at most this many waves per SIMD (0 = occupancy limit)
  *   "stack_lds"    FAST stack entries per lane kept in LDS, deeper ones in HBM (0 auto)
- *   "sun_skip", "sun_any", "fixed_point", "sun_cache"  exact shortcuts of the shading loop (1 = on) */
+ *   "sun_skip", "sun_any", "fixed_point", "sun_cache"  exact shortcuts of the shading loop (1 = on)
+ *   "denoise_lds"  the denoise filter's pass at step 1 stages its tile and halo in LDS (0 taps from global
+ *                  memory, -1 auto: 1) -- the same frame */
 
 #ifdef __cplusplus
 extern "C" {
