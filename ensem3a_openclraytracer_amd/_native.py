@@ -36,7 +36,7 @@ EXPORTED = (
     "rt_accum_sample_map", "rt_accum_add_selected", "rt_accum_mark_device", "rt_accum_select_device",
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
-    "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
+    "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
@@ -168,6 +168,7 @@ def lib():
             "rt_debug_last_refill": (_i32, [_c_p]),
             "rt_debug_last_launch": (_i32, [_c_p]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
+            "rt_debug_fn": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
             "rt_debug_timings": (_i32, [_c_p, _c_p]),
@@ -502,6 +503,22 @@ class Context:
         yy = f32(y) if y is not None else None
         out = np.zeros_like(x)
         self._check(lib().rt_debug_math(self.handle, int(fn), ptr(x), ptr(yy), out.ctypes.data, x.size))
+        return out
+
+    # rt_debug_fn's functions (rt_debug.h): name -> (id, input floats per item, output floats per item)
+    DEBUG_FN = {"camera": (0, 11, 3), "sun": (1, 5, 3), "hemi": (2, 6, 24), "ggx": (3, 13, 3), "ibl": (4, 4, 6),
+                "mt_ref": (5, 24, 2), "mt_fast": (6, 24, 2), "box_ref": (7, 12, 1), "box_fast": (8, 13, 3)}
+
+    def debug_fn(self, name: str, items) -> np.ndarray:
+        """rt_debug_fn: one call of the kernels' own device function ``name`` per row of ``items``
+        (float32[n, input floats]; integer words as their bit patterns); returns float32[n, output floats]."""
+        fn, wi, wo = self.DEBUG_FN[name]
+        x = f32(items)
+        if x.ndim != 2 or x.shape[1] != wi:
+            raise ValueError(f"{name}: items must be [n, {wi}] floats")
+        out = np.zeros((x.shape[0], wo), dtype=np.float32)
+        if x.shape[0]:
+            self._check(lib().rt_debug_fn(self.handle, fn, ptr(x), out.ctypes.data, x.shape[0]))
         return out
 
     def debug_trace(self, rays, traversal: int):

@@ -1730,6 +1730,32 @@ int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* ou
     return RT_OK;
 }
 
+int rt_debug_fn(rt_ctx* ctx, int fn, const float* in, float* out, int64_t n) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    const int wi = rt::debug_fn_in(fn), wo = rt::debug_fn_out(fn);
+    if (wi == 0) return set_err(ctx, RT_ERR_ARG, "no device function %d", fn);
+    if (!in || !out || n < 0 || n > INT32_MAX) return set_err(ctx, RT_ERR_ARG, "bad arguments");
+    if (fn == RT_FN_IBL && !ctx->have_env) return set_err(ctx, RT_ERR_STATE, "no environment");
+    if (fn == RT_FN_CAMERA)   // camera_dir divides by the width (check_frame's condition on a frame's cam)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(in[wi * i + 6] >= 1.0f && in[wi * i + 6] < 2147483648.0f))
+                return set_err(ctx, RT_ERR_ARG, "item %lld: width %g", (long long)i, (double)in[wi * i + 6]);
+    if (!n) return RT_OK;
+    Device& d = ctx->devs[0];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    const size_t ibytes = (size_t)n * wi * sizeof(float);
+    const size_t obytes = ((size_t)n * wo * sizeof(float) + 15) & ~(size_t)15;
+    HIP_OR_RET(ctx, ensure(d.scratch_a, ibytes));
+    HIP_OR_RET(ctx, ensure(d.scratch_b, obytes + rt::debug_fn_scratch_bytes(fn, n)));
+    HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, in, ibytes, hipMemcpyHostToDevice, d.stream));
+    HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    HIP_OR_RET(ctx, rt::launch_debug_fn(dev_scene(ctx, d), fn, (const float*)d.scratch_a.p, (float*)d.scratch_b.p, n,
+                                        (char*)d.scratch_b.p + obytes, d.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(out, d.scratch_b.p, (size_t)n * wo * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
 int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, int64_t n) {
     if (!ctx || !rays || !out || n < 0) return set_err(ctx, RT_ERR_ARG, "bad arguments");
     if (!ctx->have_scene) return set_err(ctx, RT_ERR_STATE, "no scene");

@@ -81,6 +81,19 @@ __device__ __forceinline__ bool mt_test(const float4* __restrict__ tg, int t, rt
     return true;
 }
 
+// The REF box test, MathLib.cl:167-190, on a node's lo.xyz hi.xyz (b[0..5]): IEEE divisions, tmax >= tmin.
+__device__ __forceinline__ bool ref_box(const float* __restrict__ b, rtm_f3 o, rtm_f3 d) {
+    const float tx1 = (b[0] - o.x) / d.x, tx2 = (b[3] - o.x) / d.x;
+    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
+    const float ty1 = (b[1] - o.y) / d.y, ty2 = (b[4] - o.y) / d.y;
+    tmin = fmaxf(tmin, fminf(ty1, ty2));
+    tmax = fminf(tmax, fmaxf(ty1, ty2));
+    const float tz1 = (b[2] - o.z) / d.z, tz2 = (b[5] - o.z) / d.z;
+    tmin = fmaxf(tmin, fminf(tz1, tz2));
+    tmax = fminf(tmax, fmaxf(tz1, tz2));
+    return tmax >= tmin;
+}
+
 // ---- REF traversal: MathLib.cl:234-288 + stack.cl ----
 template <bool COUNT>
 __device__ Hit trace_ref(const DevScene& S, rtm_f3 o, rtm_f3 d, int* __restrict__ stk, int B, Cnt& c) {
@@ -95,15 +108,7 @@ __device__ Hit trace_ref(const DevScene& S, rtm_f3 o, rtm_f3 d, int* __restrict_
         --top;
         if (COUNT) { c.nodes++; c.boxes++; }
         const float* nd = S.bvh9 + 9 * curr;
-        const float tx1 = (nd[2] - o.x) / d.x, tx2 = (nd[5] - o.x) / d.x;
-        float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
-        const float ty1 = (nd[3] - o.y) / d.y, ty2 = (nd[6] - o.y) / d.y;
-        tmin = fmaxf(tmin, fminf(ty1, ty2));
-        tmax = fminf(tmax, fmaxf(ty1, ty2));
-        const float tz1 = (nd[4] - o.z) / d.z, tz2 = (nd[7] - o.z) / d.z;
-        tmin = fmaxf(tmin, fminf(tz1, tz2));
-        tmax = fminf(tmax, fmaxf(tz1, tz2));
-        if (tmax >= tmin) {
+        if (ref_box(nd + 2, o, d)) {
             const int t = (int)nd[8];
             if (t != -1) {
                 if (COUNT) c.tris++;

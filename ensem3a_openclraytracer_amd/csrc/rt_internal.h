@@ -316,5 +316,20 @@ hipError_t launch_debug_log(const DevScene& sc, const FrameParams& fp, int trave
                             unsigned int* d_work, hipStream_t stream);
 hipError_t launch_debug_trace(const DevScene& sc, int traversal, const float* rays, float* out, int64_t n,
                               hipStream_t stream);
+// rt_debug_fn (rt_debug.h lists the functions and their items; kernels in rt_debug_fn.hip's translation unit):
+// floats per input / output item of function fn (0: no such function), the device scratch a launch over n items
+// needs (16-byte aligned), and the launch over device arrays
+constexpr int kDebugFns = 9;
+constexpr int debug_fn_in(int fn) {
+    constexpr int w[kDebugFns] = {11, 5, 6, 13, 4, 24, 24, 12, 13};
+    return fn >= 0 && fn < kDebugFns ? w[fn] : 0;
+}
+constexpr int debug_fn_out(int fn) {
+    constexpr int w[kDebugFns] = {3, 3, 24, 3, 6, 2, 2, 1, 3};
+    return fn >= 0 && fn < kDebugFns ? w[fn] : 0;
+}
+size_t debug_fn_scratch_bytes(int fn, int64_t n);
+hipError_t launch_debug_fn(const DevScene& sc, int fn, const float* in, float* out, int64_t n, void* scratch,
+                           hipStream_t stream);
 
 }  // namespace rt

@@ -47,6 +47,34 @@ int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* ou
  * triangle index (-1 = miss). */
 int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, int64_t n);
 
+/* Evaluate one of the render kernels' own shading and hit functions (rt_device.h: the functions the kernels
+ * call, not restatements of them) once per item on device 0.  in holds n items of the function's input
+ * floats, out receives n items of its output floats; words marked "bits" carry a 32-bit integer's bit pattern.
+ *   fn                in (floats per item)                        out (floats per item)
+ *   RT_FN_CAMERA      cam[10], pixel index bits (11)              camera_dir of make_const's constants (3)
+ *   RT_FN_SUN         env[5] (5)                                  make_const's sun vector (3)
+ *   RT_FN_HEMI        n.xyz, material type 1 or 2, the two RNG    hemi_cosine, hemi_uniform, hemi_sample(true),
+ *                     words bits in the samplers' argument        hemi_sample(false), each dir.xyz, invPdf and the
+ *                     order (6)                                   two RNG words after, bits (24); all four on the
+ *                                                                 frame prep_frames_kernel computes for a triangle
+ *                                                                 of normal n and a material of that type
+ *   RT_FN_GGX         colour.rgb, roughness, v, l, n (13)         brdf_ggx (3)
+ *   RT_FN_IBL         dir.xyz, power (4)                          sample_ibl, then sample_ibl_if(power), on the
+ *                                                                 environment rt_set_env uploaded (6)
+ *   RT_FN_MT_REF      a.p | 0, e1 | 0, e2 | 0 (the triangle       mt_test: hit 1 / 0, k (1000 on a miss) (2)
+ *   RT_FN_MT_FAST     records' three float4), dir.xyz, origin     mt_core: hit 1 / 0, k as computed (2)
+ *                     .xyz, 6 unused (24)
+ *   RT_FN_BOX_REF     dir, origin, lo.xyz, hi.xyz (12)            the REF traversal's box test ref_box, 1 / 0 (1)
+ *   RT_FN_BOX_FAST    dir, origin, lo.xyz, hi.xyz, cull (13)      box_hit(slab(...), cull) with the inverses
+ *                                                                 dev_recip(dir) of the FAST walks: 1 / 0, tmin,
+ *                                                                 tmax (3)
+ * RT_FN_IBL needs an environment; no function needs a scene. */
+enum {
+    RT_FN_CAMERA = 0, RT_FN_SUN = 1, RT_FN_HEMI = 2, RT_FN_GGX = 3, RT_FN_IBL = 4, RT_FN_MT_REF = 5,
+    RT_FN_MT_FAST = 6, RT_FN_BOX_REF = 7, RT_FN_BOX_FAST = 8, RT_FN_COUNT = 9
+};
+int rt_debug_fn(rt_ctx* ctx, int fn, const float* in, float* out, int64_t n);
+
 /* Render pixel `pixel` of the frame and record its path events (16 floats
  * each: kind 1 bounce ray / 2 sun ray / 3 sample end, j, o.xyz, d.xyz, k or
  * -1, material, sampleOut.xyz, 0,0,0), up to cap events, on device 0. */
