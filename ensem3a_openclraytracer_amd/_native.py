@@ -38,7 +38,7 @@ EXPORTED = (
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
-    "rt_debug_brute_clusters", "rt_debug_brute_slices", "rt_debug_last_slices",
+    "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_slices", "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
@@ -47,7 +47,7 @@ EXPORTED = (
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
              "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout",
-             "rt_debug_brute_clusters")
+             "rt_debug_brute_clusters", "rt_debug_brute_shell")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -162,6 +162,8 @@ def lib():
                                              _c_p]),
             "rt_debug_brute_clusters": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32,
                                                _c_p, _i64, _c_p, _i64, _c_p]),
+            "rt_debug_brute_shell": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32,
+                                            _c_p, _i64, _c_p]),
             "rt_debug_brute_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _c_p]),
             "rt_debug_last_slices": (_i32, []),
             "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
@@ -633,6 +635,34 @@ def brute_clusters(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, lay
     return slots.reshape(-1, 8), rows.reshape(-1, 8), int(info[1])
 
 
+SHELL_REC_FLOATS = 20   # rt_debug_brute_shell's record: the box, two counts, two records for each of six faces
+
+
+def brute_shell(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: int = -1, layout: int = RT_BVH_SAH):
+    """rt_debug_brute_shell (include/rt_debug.h): the shell option "brute_shell" = shell uploads for the scene
+    clustered with "brute_cluster" = cluster, on the host alone.  Returns None when there is no shell, else a dict:
+    ``box`` (float32 lo.x hi.x lo.y hi.y lo.z hi.z), ``faces`` (int32 [6, 2]: the two records of the faces -x +x
+    -y +y -z +z, -1 -1 where absent), ``nfaces``, ``nrest`` and ``rest`` (the slots of the singles that are no
+    face, as brute_layout's, padding included)."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    H = host_lib()
+    info = np.zeros(3, np.int64)
+    args = (ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size, ptr(b), b.size, int(layout),
+            int(cluster), int(shell))
+    st = H.rt_debug_brute_shell(*args, None, 0, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    if int(info[0]) == 0:
+        return None
+    rec = np.zeros(int(info[2]), np.float32)
+    st = H.rt_debug_brute_shell(*args, rec.ctypes.data, rec.size, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    ints = rec[:SHELL_REC_FLOATS].view(np.int32)
+    return dict(box=rec[:6].copy(), nrest=int(ints[6]), nfaces=int(ints[7]), faces=ints[8:20].reshape(6, 2).copy(),
+                rest=rec[SHELL_REC_FLOATS:].reshape(-1, 8).copy())
+
+
 def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: int = -1):
     """rt_debug_brute_slices (include/rt_debug.h): ``(on, K, tail)`` of the sample-slice rule for brute-force
     scenes, evaluated on the host alone."""
@@ -669,14 +699,15 @@ def last_refill():
 
 
 LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide", "brute", "ts", "acc",
-                 "team", "walk_team", "slices", "refill", "grid", "lds")
+                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell")
 BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
 BRUTE_REFILL = 8
 
 
 def last_launch() -> dict:
     """rt_debug_last_launch (include/rt_debug.h): the kernel key of the last render launch and the team sizes,
-    slice word, refill threshold, grid and LDS bytes its kernel got, by name (``LAUNCH_FIELDS``)."""
+    slice word, refill threshold, grid and LDS bytes its kernel got and whether it walked a shell, by name
+    (``LAUNCH_FIELDS``)."""
     out = np.zeros(len(LAUNCH_FIELDS), np.int32)
     st = lib().rt_debug_last_launch(out.ctypes.data)
     if st != 0:

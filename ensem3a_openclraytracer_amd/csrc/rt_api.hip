@@ -103,6 +103,7 @@ struct rt_ctx {
     int bvh_layout = RT_BVH_SAH;
     int brute_max = RT_BRUTE_MAX_DEFAULT;
     int brute_cluster = -1;  // brute force: clustered leaf boxes (0 off, 1 force, -1 auto; option "brute_cluster")
+    int brute_shell = -1;    // ... and the shell among their single slots (0 off, 1 force, -1 auto; option "brute_shell")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
     int walk_team = 0;  // tree walk (BVH2 item steps): lanes per pixel walking each ray together, 0 = auto
@@ -205,6 +206,15 @@ hipError_t upload(DevBuf& b, const std::vector<T>& v, hipStream_t s) {
     return hipMemcpyAsync(b.p, v.data(), bytes, hipMemcpyHostToDevice, s);
 }
 
+// DevScene::brute_cbox: the clustered slots, then the shell's record and slots (DevScene::shell)
+hipError_t upload_cbox(Device& d, const HostScene& hs) {
+    if (hs.brute_shell.empty()) return upload(d.brute_cbox, hs.brute_cbox, d.stream);
+    std::vector<float> v(hs.brute_cbox);
+    v.insert(v.end(), hs.brute_shell.begin(), hs.brute_shell.end());
+    const hipError_t e = upload(d.brute_cbox, v, d.stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(d.stream);   // v leaves scope: the copy is done first
+}
+
 int effective_traversal(const rt_ctx* ctx) {
     return (ctx->traversal == RT_TRAVERSAL_FAST && ctx->hs.fast_ok) ? RT_TRAVERSAL_FAST : RT_TRAVERSAL_REF;
 }
@@ -254,6 +264,7 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
     s.cluster_auto = ctx->brute_cluster < 0 ? 1 : 0;
     s.nsingle = ctx->hs.nsingle;
+    s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
     s.stack_lds = std::min<int32_t>(s.depth > 0 ? s.depth : 1,
                                     ctx->stack_lds > 0 ? ctx->stack_lds : wide ? rt::kStackLdsWide : rt::kStackLds);
     s.stack_ovf = (int2*)d.stack_ovf.p;
@@ -398,7 +409,8 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         invalidate_accum(ctx);
         return RT_OK;
     }
-    if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max") || !std::strcmp(key, "brute_cluster")) {
+    if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max") || !std::strcmp(key, "brute_cluster") ||
+        !std::strcmp(key, "brute_shell")) {
         if (!std::strcmp(key, "bvh")) {
             if (value != RT_BVH_REFERENCE && value != RT_BVH_SAH)
                 return set_err(ctx, RT_ERR_ARG, "bvh must be 0 (reference tree) or 1 (sah)");
@@ -407,6 +419,10 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
             if (value < -1 || value > 1)
                 return set_err(ctx, RT_ERR_ARG, "brute_cluster must be -1 (auto), 0 (off) or 1 (force)");
             ctx->brute_cluster = (int)value;
+        } else if (!std::strcmp(key, "brute_shell")) {
+            if (value < -1 || value > 1)
+                return set_err(ctx, RT_ERR_ARG, "brute_shell must be -1 (auto), 0 (off) or 1 (force)");
+            ctx->brute_shell = (int)value;
         } else {
             if (value < 0 || value > 4096) return set_err(ctx, RT_ERR_ARG, "brute_max must be in 0..4096");
             ctx->brute_max = (int)value;
@@ -414,7 +430,8 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
         if (!ctx->have_scene) return RT_OK;
         HostScene& hs = ctx->hs;   // repack the FAST nodes of the current scene
         std::string why;
-        rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster, why);
+        rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster,
+                         ctx->brute_shell, why);
         for (auto& d : ctx->devs) {
             HIP_OR_RET(ctx, hipSetDevice(d.id));
             HIP_OR_RET(ctx, order_after_last(d, d.stream));
@@ -425,7 +442,7 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
             HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
             HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
             HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
-            HIP_OR_RET(ctx, upload(d.brute_cbox, hs.brute_cbox, d.stream));
+            HIP_OR_RET(ctx, upload_cbox(d, hs));
             HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
             HIP_OR_RET(ctx, upload(d.tri_geo, hs.tri_geo, d.stream));
             HIP_OR_RET(ctx, upload(d.tri_fast, hs.tri_fast, d.stream));
@@ -564,7 +581,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     HostScene hs;
     std::string msg, why;
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, ctx->bvh_layout,
-                                     ctx->brute_max, ctx->brute_cluster, msg, why);
+                                     ctx->brute_max, ctx->brute_cluster, ctx->brute_shell, msg, why);
     if (rc != RT_OK) return set_err(ctx, rc, "%s", msg.c_str());
     invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
@@ -578,7 +595,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
         HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
         HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
         HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
-        HIP_OR_RET(ctx, upload(d.brute_cbox, hs.brute_cbox, d.stream));
+        HIP_OR_RET(ctx, upload_cbox(d, hs));
         HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
         HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
         HIP_OR_RET(ctx, upload(d.bvh9, hs.bvh9, d.stream));
@@ -1824,13 +1841,14 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 
 int rt_debug_last_slices(void) { return rt::last_launch().slices; }
 
-int rt_debug_last_launch(int32_t out[17]) {
+int rt_debug_last_launch(int32_t out[18]) {
     if (!out) return RT_ERR_ARG;
     const rt::LaunchNote n = rt::last_launch();
     const rt::KernelKey& k = n.key;
-    const int64_t v[17] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
-                           k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds};
-    for (int i = 0; i < 17; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    const int64_t v[18] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
+                           k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds,
+                           n.shell};
+    for (int i = 0; i < 18; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
     return RT_OK;
 }
 

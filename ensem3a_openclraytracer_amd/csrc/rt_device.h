@@ -601,7 +601,49 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         const unsigned* besthi = reinterpret_cast<const unsigned*>(bestk) + 1;              // distance bits of bestk[i] at [2 i]
         inv[lane] = ix; inv[64 + lane] = iy; inv[128 + lane] = iz;
         const ConstF4 cb = as_const(S.brute_cbox);
-        lockstep(cb, 0, S.nsingle);
+        // The shell (DevScene::shell, scene_pack.cpp build_shell): the single slots that are faces of one box --
+        // a room's walls -- share its six planes.  Their distances and each axis's min / max are computed once;
+        // a face's test is then slab()'s two nests in slab()'s order and box_hit(), with the flat axis's one
+        // distance standing for both its min and its max: fminf(t, t) = fmaxf(t, t) = t, a NaN t is dropped by
+        // the same nest that drops it in slab(), so tn and tx are slab()'s bits on the face's own box.  All six
+        // tests come before the enqueues and cull with the best hit as of here, as group does.  The singles that
+        // are no face follow in a slot array of their own
+        ConstF4 sb = cb;
+        int ns = S.nsingle;
+        if (S.shell) {
+            const ConstF4 sh{cb.p + 4 * S.shell};
+            const float4 h0 = sgpr4(sh[0]), h1 = sgpr4(sh[1]), fx = sgpr4(sh[2]), fy = sgpr4(sh[3]), fz = sgpr4(sh[4]);
+            const float cull = bk * CULL_MARGIN;
+            const float x0 = (h0.x - o.x) * ix, x1 = (h0.y - o.x) * ix;
+            const float y0 = (h0.z - o.y) * iy, y1 = (h0.w - o.y) * iy;
+            const float z0 = (h1.x - o.z) * iz, z1 = (h1.y - o.z) * iz;
+            const float t[6] = {x0, x1, y0, y1, z0, z1};
+            const float mn[3] = {fminf(x0, x1), fminf(y0, y1), fminf(z0, z1)};
+            const float mx[3] = {fmaxf(x0, x1), fmaxf(y0, y1), fmaxf(z0, z1)};
+            // the records of the faces -x +x -y +y -z +z (an absent face: -1 -1, skipped by the wave-uniform
+            // branch around its enqueue: the compiler sinks each face's test -- v_max, v_min, v_max3, v_min3,
+            // v_cmp -- to its one use there, so the pass mask goes from vcc straight into the enqueue).  A
+            // branch of its own around each test, ahead of the enqueues, measured slower on C2's five faces
+            // (r15, DESIGN.md 5.2: 6.16-6.18 against 6.02-6.03 ms): six more compare-and-branch pairs, and
+            // every pass mask is kept in an SGPR pair until its enqueue
+            const int q[12] = {__float_as_int(fx.x), __float_as_int(fx.y), __float_as_int(fx.z), __float_as_int(fx.w),
+                               __float_as_int(fy.x), __float_as_int(fy.y), __float_as_int(fy.z), __float_as_int(fy.w),
+                               __float_as_int(fz.x), __float_as_int(fz.y), __float_as_int(fz.z), __float_as_int(fz.w)};
+            bool pass[6];
+#pragma unroll
+            for (int f = 0; f < 6; ++f) {
+                const int a = f >> 1;
+                const float tn = fmaxf(fmaxf(a == 0 ? t[f] : mn[0], a == 1 ? t[f] : mn[1]), a == 2 ? t[f] : mn[2]);
+                const float tx = fminf(fminf(a == 0 ? t[f] : mx[0], a == 1 ? t[f] : mx[1]), a == 2 ? t[f] : mx[2]);
+                pass[f] = box_hit(tn, tx, cull);
+            }
+#pragma unroll
+            for (int f = 0; f < 6; ++f)
+                if (q[2 * f] >= 0) enqueue(pass[f], (unsigned)q[2 * f], q[2 * f + 1]);
+            sb = ConstF4{sh.p + kShellRecF};
+            ns = __float_as_int(h1.z);
+        }
+        lockstep(sb, 0, ns);
         unsigned ihead = 0, itail = 0;   // wave-uniform item positions; itail is a multiple of kClusterSlots
         // one batch of n <= nact items: fewer than nact pairs are queued before it and it adds at most 2 n
         auto run_items = [&](int n) __attribute__((always_inline)) {

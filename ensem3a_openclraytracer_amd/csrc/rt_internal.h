@@ -86,6 +86,11 @@ struct DevScene {
     // padding slots stay in memory -- a group load never leaves the buffer, an item's slot index is a shift and
     // a mask -- but only an item tests one
     int32_t nsingle;
+    // the shell (scene_pack.cpp build_shell, option "brute_shell"): where its record starts in brute_cbox, in
+    // float4 (behind the ncslot slots: 5 float4, then the slots of the singles that are no face); 0: no shell, the
+    // clustered loop tests the single slots [0, nsingle).  (It stands where the structure had padding: no other
+    // field moves, and no kernel's arguments do.)
+    int32_t shell;
 };
 
 struct FrameParams {
@@ -308,6 +313,7 @@ struct LaunchNote {
     int team, walk_team, slices, refill;
     int64_t grid;
     size_t lds;
+    int shell;   // the kernel walks the scene's shell (the clustered loop, DevScene::shell != 0)
 };
 void note_launch(const LaunchNote& n);
 LaunchNote last_launch();

@@ -38,6 +38,15 @@ constexpr double kClusterGain = 0.75;
 // lock-step: n passing lanes cost n kClusterSlots / nact item batches against kClusterSlots lock-step
 // boxes, equal at n = nact / kappa = 0.53 nact
 constexpr int kClusterLockNum = 4;
+// The shell among a clustered scene's single slots (scene_pack.cpp build_shell, option "brute_shell"): its record
+// is kShellRecF floats (5 float4), the remaining singles' slots follow it.  auto takes a shell from kShellMinFaces
+// faces: the smallest count at which the shell piece issues fewer VALU + SALU instructions than as many single
+// tests, counted in the built gfx950 kernel: n single tests are 23 n VALU; the shell piece is 18
+// shared VALU (6 subtracts, 6 multiplies, 3 min / max pairs), up to 8 canonicalising v_max, 5 VALU per face (3
+// for the second of a -z +z pair) and 12 SALU (a compare and a branch per face position) -- at most 48 against 46
+// for two faces, at most 53 against 69 for three
+constexpr int kShellRecF = 20;
+constexpr int kShellMinFaces = 3;
 #ifndef RT_BRUTE_MAX_DEFAULT
 #define RT_BRUTE_MAX_DEFAULT 64   // FAST tests every triangle of scenes up to this size (rt_set_option "brute_max")
 #endif

@@ -502,13 +502,129 @@ void build_clusters(HostScene& hs, int mode) {
     hs.nsingle = (int32_t)singles.size();
 }
 
+// The shell of a clustered scene (HostScene::brute_shell; option "brute_shell", mode 0 off, < 0 auto, > 0 force):
+// a box S with lo < hi, finite, on every axis, and the single slots that are faces of it -- a slot is a face when
+// its box is flat on one axis at S's lower or upper bound there and equals S's range on the other two, every
+// equality bitwise (-0 is not +0).  The walls of an axis-aligned room are such slots: their 6 bounds each are
+// drawn from S's 6, so the kernel computes S's six plane distances once per ray and tests each face from them
+// (rt_device.h trace_brute_compact).  Two faces fix S, so every shell of two or more faces is the S of some pair
+// of flat singles: perpendicular ones (each lies on an end of the other's range along its flat axis, and their
+// ranges on the third axis agree) or parallel ones (the same ranges on the other two axes).  The S with the most
+// faces is taken; among equals the one whose faces' slots, in ascending order, compare lowest, then the lowest
+// bounds' bits.  A face position holds the first slot that fits (bit-identical boxes share a slot, so a second
+// one is a third coplanar record: it stays a single).  auto: only from kShellMinFaces faces; force: from the two
+// that define a shell.  brute_cbox, brute_crow and nsingle are untouched; the singles that are no face are copied
+// behind the record in their order.
+void build_shell(HostScene& hs, int mode) {
+    hs.brute_shell.clear();
+    hs.nshell = 0;
+    hs.nrest = 0;
+    if (mode == 0 || hs.ncluster == 0) return;
+    const int32_t n = hs.nsingle;
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return u;
+    };
+    auto same = [&](float a, float b) { return bits(a) == bits(b); };
+    auto box = [&](int32_t s) { return hs.brute_cbox.data() + 8 * (size_t)s; };
+    // the axis a slot is flat on, when it is flat on one axis alone and a proper finite range on the others
+    std::vector<int> flat((size_t)n, -1);
+    for (int32_t s = 0; s < n; ++s) {
+        const float* b = box(s);
+        int nf = 0, ax = -1;
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) {
+            ok = ok && std::isfinite(b[2 * a]) && std::isfinite(b[2 * a + 1]);
+            if (same(b[2 * a], b[2 * a + 1])) { ++nf; ax = a; }
+            else ok = ok && b[2 * a] < b[2 * a + 1];
+        }
+        if (ok && nf == 1) flat[s] = ax;
+    }
+    typedef std::array<uint32_t, 6> Key;          // S's bounds' bits, lo.x hi.x lo.y hi.y lo.z hi.z
+    std::map<Key, std::array<int32_t, 6>> shells;   // -> the slot at each face position -x +x -y +y -z +z, or -1
+    auto add_face = [&](std::array<int32_t, 6>& f, const float* S, int32_t s) {
+        const int a = flat[s];
+        const int pos = 2 * a + (same(box(s)[2 * a], S[2 * a]) ? 0 : 1);
+        if (f[pos] < 0 || s < f[pos]) f[pos] = s;
+    };
+    for (int32_t s = 0; s < n; ++s) {
+        if (flat[s] < 0) continue;
+        for (int32_t t = s + 1; t < n; ++t) {
+            if (flat[t] < 0) continue;
+            const float *p = box(s), *q = box(t);
+            const int a = flat[s], b = flat[t];
+            float S[6];
+            if (a == b) {
+                bool ok = !same(p[2 * a], q[2 * a]);
+                for (int k = 0; k < 3; ++k)
+                    if (k != a) ok = ok && same(p[2 * k], q[2 * k]) && same(p[2 * k + 1], q[2 * k + 1]);
+                if (!ok) continue;
+                for (int k = 0; k < 6; ++k) S[k] = p[k];
+                S[2 * a] = std::min(p[2 * a], q[2 * a]);
+                S[2 * a + 1] = std::max(p[2 * a], q[2 * a]);
+                if (!(S[2 * a] < S[2 * a + 1])) continue;   // -0 and +0: no range
+            } else {
+                const int c = 3 - a - b;
+                if (!(same(p[2 * a], q[2 * a]) || same(p[2 * a], q[2 * a + 1]))) continue;
+                if (!(same(q[2 * b], p[2 * b]) || same(q[2 * b], p[2 * b + 1]))) continue;
+                if (!(same(p[2 * c], q[2 * c]) && same(p[2 * c + 1], q[2 * c + 1]))) continue;
+                S[2 * a] = q[2 * a]; S[2 * a + 1] = q[2 * a + 1];
+                S[2 * b] = p[2 * b]; S[2 * b + 1] = p[2 * b + 1];
+                S[2 * c] = p[2 * c]; S[2 * c + 1] = p[2 * c + 1];
+            }
+            Key key;
+            for (int k = 0; k < 6; ++k) key[k] = bits(S[k]);
+            auto it = shells.find(key);
+            if (it == shells.end()) it = shells.emplace(key, std::array<int32_t, 6>{-1, -1, -1, -1, -1, -1}).first;
+            add_face(it->second, S, s);
+            add_face(it->second, S, t);
+        }
+    }
+    const Key* best = nullptr;
+    std::vector<int32_t> best_slots;
+    for (const auto& kv : shells) {
+        std::vector<int32_t> slots;
+        for (int32_t s : kv.second)
+            if (s >= 0) slots.push_back(s);
+        std::sort(slots.begin(), slots.end());
+        if (!best || slots.size() > best_slots.size() || (slots.size() == best_slots.size() && slots < best_slots)) {
+            best = &kv.first;
+            best_slots = slots;
+        }
+    }
+    const int need = mode < 0 ? rt::kShellMinFaces : 2;
+    if (!best || (int)best_slots.size() < need) return;
+    const std::array<int32_t, 6>& face = shells[*best];
+    const int32_t nrest = n - (int32_t)best_slots.size();
+    const size_t nr4 = ((size_t)nrest + rt::kBoxGroup - 1) / rt::kBoxGroup * rt::kBoxGroup;
+    hs.brute_shell.assign(rt::kShellRecF + 8 * nr4, 0.0f);
+    float* r = hs.brute_shell.data();
+    for (int k = 0; k < 6; ++k) std::memcpy(r + k, &(*best)[k], 4);
+    r[6] = as_f32(nrest);
+    r[7] = as_f32((int32_t)best_slots.size());
+    for (int f = 0; f < 6; ++f) {
+        r[8 + 2 * f] = face[f] < 0 ? as_f32(-1) : box(face[f])[6];
+        r[9 + 2 * f] = face[f] < 0 ? as_f32(-1) : box(face[f])[7];
+    }
+    float* o = r + rt::kShellRecF;
+    for (size_t s = 0; s < nr4; ++s) pad_box(o + 8 * s);
+    for (int32_t s = 0; s < n; ++s)
+        if (!std::binary_search(best_slots.begin(), best_slots.end(), s)) {
+            std::memcpy(o, box(s), 8 * sizeof(float));
+            o += 8;
+        }
+    hs.nshell = (int32_t)best_slots.size();
+    hs.nrest = nrest;
+}
+
 // Pack the FAST layout from the reference export.  Returns false (with
 // reason) if the export is not a proper binary tree with one triangle per
 // leaf, in which case only the REF traversal is available.  layout
 // RT_BVH_REFERENCE keeps the reference's tree, RT_BVH_SAH regroups its leaf
 // boxes (bvh_sah.cpp); both give the same hits.
 bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int layout, int brute_max, int cluster,
-               std::string& why) {
+               int shell, std::string& why) {
     if (nn <= 0) {
         why = "empty BVH";
         return false;
@@ -587,6 +703,9 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
     hs.brute_crow.clear();
     hs.ncluster = 0;
     hs.nsingle = 0;
+    hs.brute_shell.clear();
+    hs.nshell = 0;
+    hs.nrest = 0;
     if ((int64_t)leaves.size() <= (int64_t)brute_max) {
         std::vector<int32_t> by_rank(leaves.size());
         for (int32_t n : leaves) by_rank[rank[T[n]]] = n;
@@ -640,6 +759,7 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
             }
         }
         build_clusters(hs, cluster);
+        build_shell(hs, shell);
     }
     if (layout == RT_BVH_SAH && leaves.size() > 1) {
         std::vector<float> lb(6 * leaves.size());
@@ -666,8 +786,8 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
 namespace rt {
 
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
-                  std::string& why) {
-    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, why) : true;
+                  int shell, std::string& why) {
+    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, shell, why) : true;
     if (hs.fast_ok && ntri > 0) {
         // the FAST kernels' Moller-Trumbore reciprocal (rt_device.h mt_recip) is IEEE-exact for
         // |a| <= 2^126, a = e1 . (d x e2) with |d| = 1: bound |e1| |e2| (finite edges; an infinite or
@@ -692,6 +812,7 @@ void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, in
     }
     if (!hs.fast_ok) { hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0; }
     if (hs.nbrute == 0) { hs.brute_cbox.clear(); hs.brute_crow.clear(); hs.ncluster = 0; hs.nsingle = 0; }
+    if (hs.ncluster == 0) { hs.brute_shell.clear(); hs.nshell = 0; hs.nrest = 0; }
     if (!hs.fast_ok || hs.wdepth > 64) { hs.wnodes.clear(); hs.wleaves.clear(); hs.nwnodes = 0; hs.wdepth = 1; }
     // render kernels keep kStackLds entries in LDS and spill deeper ones to HBM; the single-ray
     // debug kernel keeps the whole stack in LDS (int2 entries, 128 lanes): depth <= 64
@@ -711,7 +832,7 @@ namespace {
 
 int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                    int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                   int brute_max, int cluster, std::string& msg, std::string& why) {
+                   int brute_max, int cluster, int shell, std::string& msg, std::string& why) {
     if (nvp < 0 || nvp % 3 || nvn < 0 || nvn % 3 || nface < 0 || nface % 10 || nmat <= 0 || nmat % 6 || nbvh < 0 ||
         nbvh % 9)
         return fail(msg, RT_ERR_ARG,
@@ -788,7 +909,7 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
             }
         }
     }
-    pack_checked(hs, bvh9, NB, T, layout, brute_max, cluster, why);
+    pack_checked(hs, bvh9, NB, T, layout, brute_max, cluster, shell, why);
     return RT_OK;
 }
 
@@ -797,10 +918,10 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
 // No C++ exception leaves the C ABI: a scene too large for host memory is an error status.
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, int cluster, std::string& msg, std::string& why) {
+                  int brute_max, int cluster, int shell, std::string& msg, std::string& why) {
     try {
-        return scene_prepare_(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout, brute_max, cluster, msg,
-                              why);
+        return scene_prepare_(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout, brute_max, cluster, shell,
+                              msg, why);
     } catch (const std::bad_alloc&) {
         hs = HostScene();
         return fail(msg, RT_ERR_ARG, "scene too large for host memory");
@@ -826,7 +947,7 @@ extern "C" int rt_scene_check(const float* vp, int64_t nvp, const float* vn, int
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, -1, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc == RT_OK && info) {
         info[0] = hs.ntri;
@@ -857,7 +978,7 @@ extern "C" int rt_debug_brute_layout(const float* vp, int64_t nvp, const float* 
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, -1, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.nbox;
@@ -887,7 +1008,7 @@ extern "C" int rt_debug_brute_clusters(const float* vp, int64_t nvp, const float
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, cluster, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, cluster, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.ncluster;
@@ -897,5 +1018,34 @@ extern "C" int rt_debug_brute_clusters(const float* vp, int64_t nvp, const float
     const int64_t ns = std::min<int64_t>(slot_cap, info[2]), nr = std::min<int64_t>(row_cap, info[3]);
     if (ns > 0) std::memcpy(slots, hs.brute_cbox.data(), (size_t)ns * sizeof(float));
     if (nr > 0) std::memcpy(rows, hs.brute_crow.data(), (size_t)nr * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_brute_shell(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                    int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                    int layout, int cluster, int shell, float* rec, int64_t cap, int64_t info[3]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (cluster < -1 || cluster > 1 || shell < -1 || shell > 1) {
+        g_check_error = "brute_cluster and brute_shell must be -1 (auto), 0 (off) or 1 (force)";
+        return RT_ERR_ARG;
+    }
+    if (!info || cap < 0 || (cap > 0 && !rec)) {
+        g_check_error = "null info, or a capacity without an array";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[0] = hs.nshell;
+    info[1] = hs.nrest;
+    info[2] = (int64_t)hs.brute_shell.size();
+    const int64_t n = std::min<int64_t>(cap, info[2]);
+    if (n > 0) std::memcpy(rec, hs.brute_shell.data(), (size_t)n * sizeof(float));
     return RT_OK;
 }

@@ -31,6 +31,12 @@ struct HostScene {
     std::vector<float> brute_cbox; // 8 floats per slot: the single slots padded to whole groups, then kClusterSlots per cluster
     std::vector<float> brute_crow; // 8 floats per cluster: union lo.x hi.x lo.y hi.y lo.z hi.z | first slot, box count
     int32_t ncluster = 0, nsingle = 0;   // clusters; single (real) slots at the head of brute_cbox
+    // the shell among the single slots (scene_pack.cpp build_shell, option "brute_shell"; nshell = 0: none):
+    // kShellRecF floats -- the shell box lo.x hi.x lo.y hi.y | lo.z hi.z, nrest, nshell (int bits) | the two
+    // records of the faces -x +x | -y +y | -z +z (int bits; an absent face -1 -1) -- then the nrest singles that
+    // are no face, 8 floats per slot in brute_cbox order, padded to whole groups
+    std::vector<float> brute_shell;
+    int32_t nshell = 0, nrest = 0;       // faces of the shell; single slots outside it
     int32_t nnodes = 0, root_ref = 0, ntri = 0, nmat = 0, nbvh9 = 0, depth = 1;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     bool fast_ok = false;
@@ -44,11 +50,11 @@ struct HostScene {
 // reason when the FAST layouts are unavailable (hs.fast_ok false; the REF traversal then serves).
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, int cluster, std::string& msg, std::string& why);
+                  int brute_max, int cluster, int shell, std::string& msg, std::string& why);
 
 // pack_fast + the limits of the FAST kernels; sets hs.fast_ok (an option change repacks with it).
-// cluster: option "brute_cluster" (0 off, -1 auto, 1 force; include/rt_debug.h).
+// cluster, shell: options "brute_cluster", "brute_shell" (0 off, -1 auto, 1 force; include/rt_debug.h).
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
-                  std::string& why);
+                  int shell, std::string& why);
 
 }  // namespace rt

@@ -15,6 +15,8 @@
  *   "team"         brute force: lanes per pixel 1/2/4/8 (0 auto by tile size)
  *   "brute_cluster"  brute force, one lane per pixel: groups of leaf boxes behind one union test, the passing
  *                  rays' (ray, box) tests compacted (0 off, 1 every SAH subtree of 2..8 boxes, -1 auto by cost)
+ *   "brute_shell"  clustered brute force: the single boxes that are faces of one box (a room's walls) are tested
+ *                  from its six plane distances, computed once per ray (0 off, 1 from two faces, -1 auto from three)
  *   "brute_refill" brute force, one lane per pixel: a wave hands out jobs once this many lanes are free, 2..64
  *                  (0 or 1 every free lane at once, -1 auto: 4 on tiles of >= 1.5 pixels per resident lane)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
@@ -137,6 +139,19 @@ int rt_debug_brute_clusters(const float* V_p, int64_t n_vp, const float* V_n, in
                             int layout, int cluster, float* slots, int64_t slot_cap, float* rows, int64_t row_cap,
                             int64_t info[4]);
 
+/* Host-only (no device): the shell that option "brute_shell" = shell (-1 auto, 0 off, 1 force) makes rt_set_scene
+ * upload for a scene clustered with "brute_cluster" = cluster: a box S and the single slots of
+ * rt_debug_brute_clusters' array that are faces of it -- flat on one axis at S's lower or upper bound, S's range
+ * on the other two, every equality bitwise.  The kernels of the clustered loop test the faces from S's six plane
+ * distances, computed once per ray, and the other singles from a slot array of their own.  info[0] = faces (0: no
+ * shell, the array is empty; auto takes a shell from 3 faces, force from the 2 that define one), info[1] = single slots that are no face,
+ * info[2] = floats in the array: 20 for the record -- S as lo.x hi.x lo.y hi.y lo.z hi.z, the int bits of info[1]
+ * and info[0], then the int bits of the two records of the faces -x, +x, -y, +y, -z, +z (-1 -1: no such face) --
+ * then 8 per remaining single, in their order, padded to a whole group of 4 as above. */
+int rt_debug_brute_shell(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                         int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                         int layout, int cluster, int shell, float* rec, int64_t cap, int64_t info[3]);
+
 /* No device call: the rule for sample slices on a brute-force scene (option "slices" = option: -1 auto, 0 off,
  * K) for a launch over a tile of nloc pixels on a device that keeps `lanes` lanes of the kernel resident, which
  * brings every pixel to spp samples; accum_base >= 0: an add of a progressive accumulation that has accum_base of
@@ -154,8 +169,9 @@ int rt_debug_last_slices(void);
  * dequantisation), brute (0 none, 1 lock-step, 2 teams, 3 clustered, + 4 sample slices, + 8 refill threshold),
  * ts (lanes per pixel of the tree walk), acc (0 one-shot, 1 an add, 2 a listed add); out[11..14] = the brute-force
  * team size, the walk's team size, the slice word (rt_debug_last_slices) and R (rt_debug_last_refill) of its
- * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block. */
-int rt_debug_last_launch(int32_t out[17]);
+ * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block; out[17] = 1 when the kernel
+ * walked a shell (option "brute_shell": the clustered loop on a scene that has one), else 0. */
+int rt_debug_last_launch(int32_t out[18]);
 
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
