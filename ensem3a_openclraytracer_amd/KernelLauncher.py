@@ -227,6 +227,8 @@ class KernelLauncher(object):
         self.set_bvh(bvh)
         self._scene_key: Optional[tuple] = None
         self._env_key: Optional[tuple] = None
+        self._face_material: Optional[np.ndarray] = None
+        self._face_material_dev: dict = {}
 
     def set_traversal(self, traversal: str) -> None:
         mode = {"fast": _native.RT_TRAVERSAL_FAST, "ref": _native.RT_TRAVERSAL_REF}.get(traversal)
@@ -254,6 +256,8 @@ class KernelLauncher(object):
         if key != self._scene_key:
             self._ctx.set_scene(*arrays)
             self._scene_key = key
+            self._face_material = arrays[3].reshape(-1, 10)[:, 0].copy()   # trace_rays: a hit's material
+            self._face_material_dev = {}
 
     def _upload_env(self, h_IBL) -> None:
         img = _ibl_rgba(h_IBL)
@@ -331,6 +335,60 @@ class KernelLauncher(object):
         self._ctx.accum_begin(cam[:10], env[:5], imgDim, int(maxBounce))
         self._progressive = Progressive(self._ctx, imgDim)
         return self._progressive
+
+    def upload_scene(self, h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_BVH) -> None:
+        """Upload the scene alone (what ``launch_Raytracing`` does with these arguments): ``trace_rays`` needs
+        no environment and no frame."""
+        self._upload_scene(h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_BVH)
+
+    def trace_rays(self, origins, directions, tmax=None, any_hit: bool = False) -> dict:
+        """Trace rays of the caller's own through the uploaded scene (rt_trace of rt_api.h): the hits a frame
+        would see, under the launcher's traversal.  ``origins`` and ``directions`` are ``[n, 3]`` (directions are
+        used as given, not normalised), ``tmax`` a scalar or ``[n]`` (None: the horizon, 1000; a hit has
+        ``k < min(tmax, 1000)``).  Returns ``k`` (1000 on a miss), ``tri`` (the row of faceData, -1 on a miss),
+        ``u``, ``v`` (barycentrics, 0 on a miss), ``hit`` and ``material`` (``faceData[tri, 0]``, -1 on a miss).
+        With ``any_hit`` the flag is the closest-hit query's, and a hit describes some triangle the ray really
+        hits within ``tmax``, not necessarily the closest.
+
+        numpy arrays are traced blocking, split over the launcher's devices.  Objects with ``data_ptr()`` (torch
+        tensors on the launcher's first device) go through the device form on torch's current stream: nothing
+        is copied to the host and the call does not wait; the results are tensors on that device."""
+        if getattr(self, "_face_material", None) is None:
+            raise RuntimeError("trace_rays needs a scene: call upload_scene or launch_Raytracing first")
+        mode = _native.RT_QUERY_ANY if any_hit else _native.RT_QUERY_CLOSEST
+        if hasattr(origins, "data_ptr") or hasattr(directions, "data_ptr"):
+            return self._trace_rays_torch(origins, directions, tmax, mode)
+        hits = self._ctx.trace(_native.pack_rays(origins, directions, tmax), mode)
+        hit = hits["tri"] >= 0
+        material = np.full(len(hits), -1, np.int32)
+        material[hit] = self._face_material[hits["tri"][hit]]
+        return {"k": hits["k"].copy(), "tri": hits["tri"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(),
+                "hit": hit, "material": material}
+
+    def _trace_rays_torch(self, origins, directions, tmax, mode: int) -> dict:
+        import torch
+        dev = origins.device if hasattr(origins, "data_ptr") else directions.device
+        o = torch.as_tensor(origins, dtype=torch.float32, device=dev).reshape(-1, 3)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=dev).reshape(-1, 3)
+        if o.shape[0] != d.shape[0]:
+            raise ValueError(f"{o.shape[0]} origins but {d.shape[0]} directions")
+        n = o.shape[0]
+        rays = torch.zeros((n, _native.RAY_FLOATS), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = d
+        rays[:, 3:6] = o
+        rays[:, 6] = _native.QUERY_HORIZON if tmax is None else torch.as_tensor(tmax, dtype=torch.float32, device=dev)
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        if n:
+            self._ctx.trace_device(0, rays.data_ptr(), n, mode, out.data_ptr(),
+                                   torch.cuda.current_stream(dev).cuda_stream)
+        tri = out[:, 1].view(torch.int32)
+        hit = tri >= 0
+        table = self._face_material_dev.get(dev)
+        if table is None:
+            table = torch.as_tensor(self._face_material, dtype=torch.int32, device=dev)
+            self._face_material_dev[dev] = table
+        material = torch.where(hit, table[tri.clamp(min=0).long()] if len(table) else tri, torch.full_like(tri, -1))
+        return {"k": out[:, 0], "tri": tri, "u": out[:, 2], "v": out[:, 3], "hit": hit, "material": material}
 
     def launch_ImgProcessing(self, h_src, h_out, SIZE):
         """Gamma 2.2 of ``ImgProcessing.cl``: ``h_out[k] = min(h_src[k], 1) ** 2.2`` for ``k < 3*SIZE*SIZE``."""

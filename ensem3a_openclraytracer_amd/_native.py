@@ -36,6 +36,7 @@ EXPORTED = (
     "rt_accum_sample_map", "rt_accum_add_selected", "rt_accum_mark_device", "rt_accum_select_device",
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
+    "rt_trace", "rt_trace_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_slices", "rt_debug_last_slices",
@@ -64,6 +65,27 @@ class DenoiseParams(ctypes.Structure):
 
 
 GUIDE_FLOATS = 12   # three float4 per pixel: n | k, P | f, a | m (rt_api.h)
+
+# Ray queries (rt_trace*, rt_api.h): rt_hit, and a ray's eight floats dir.xyz, origin.xyz, tmax, reserved
+HIT_DTYPE = np.dtype([("k", np.float32), ("tri", np.int32), ("u", np.float32), ("v", np.float32)])
+RAY_FLOATS = 8
+RT_QUERY_CLOSEST = 0
+RT_QUERY_ANY = 1
+QUERY_HORIZON = 1000.0   # the reference's horizon: a hit has k < min(tmax, 1000)
+
+
+def pack_rays(origins, directions, tmax=None) -> np.ndarray:
+    """float32 ``[n, 8]`` rays of rt_trace from ``[n, 3]`` origins and directions: ``dir, origin, tmax, 0``.
+    ``tmax`` is a scalar or ``[n]``; None packs the horizon, 1000."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError(f"{len(o)} origins but {len(d)} directions")
+    rays = np.zeros((len(o), RAY_FLOATS), np.float32)
+    rays[:, 0:3] = d
+    rays[:, 3:6] = o
+    rays[:, 6] = QUERY_HORIZON if tmax is None else np.asarray(tmax, dtype=np.float32)
+    return rays
 
 
 class NativeError(RuntimeError):
@@ -149,6 +171,8 @@ def lib():
             "rt_accum_guides_device": (_i32, [_c_p, _i32, _c_p, _c_p]),
             "rt_denoise_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, ctypes.POINTER(DenoiseParams), _c_p, _c_p]),
             "rt_accum_denoise": (_i32, [_c_p, ctypes.POINTER(DenoiseParams), _c_p]),
+            "rt_trace": (_i32, [_c_p, _c_p, _i64, _i32, _c_p]),
+            "rt_trace_device": (_i32, [_c_p, _i32, _c_p, _i64, _i32, _c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -486,6 +510,24 @@ class Context:
         self._check(lib().rt_accum_denoise(self.handle, ctypes.byref(params) if params is not None else None,
                                            out.ctypes.data))
         return out
+
+    # -- ray queries (rt_trace / rt_trace_device) --
+    def trace(self, rays8, mode: int = RT_QUERY_CLOSEST) -> np.ndarray:
+        """rt_trace: ``rays8`` float32 ``[n, 8]`` (``pack_rays``) -> a ``HIT_DTYPE`` array ``[n]``, blocking."""
+        r = f32(rays8)
+        if r.size % RAY_FLOATS:
+            raise ValueError("rays must hold 8 floats each: dir.xyz, origin.xyz, tmax, reserved")
+        n = r.size // RAY_FLOATS
+        out = np.zeros(n, HIT_DTYPE)
+        self._check(lib().rt_trace(self.handle, ptr(r), n, int(mode), out.ctypes.data if n else None))
+        return out
+
+    def trace_device(self, device_index: int, rays_ptr: int, n: int, mode: int, out_ptr: int,
+                     stream_ptr: int = 0) -> None:
+        """rt_trace_device: device arrays on slot ``device_index``, enqueued on the stream; never waits."""
+        self._check(lib().rt_trace_device(self.handle, int(device_index), _c_p(int(rays_ptr)) if rays_ptr else None,
+                                          int(n), int(mode), _c_p(int(out_ptr)) if out_ptr else None,
+                                          self._stream(stream_ptr)))
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

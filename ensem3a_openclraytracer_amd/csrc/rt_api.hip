@@ -79,6 +79,9 @@ struct Device {
     // filter's scratch (X twice, N, P: 64 bytes per frame pixel) and the launch constants of the guide kernel;
     // the host forms' guides of this slot's tile; and, on the slot that filters, the frame-shaped input and output
     DevBuf dn, dn_const, guides, dn_rgb, dn_guides, dn_out;
+    // Ray queries (rt_trace*): the hand-out counter of the persistent kernels and, for the host form, this slot's
+    // rays and results -- buffers of their own, allocated on first use
+    DevBuf q_counter, q_rays, q_out;
     char* host_stage = nullptr;   // pinned staging for rt_render / rt_render_rgb8
     int* host_pick = nullptr;     // pinned: a two-pass launch's pass-2 pick, read back (rt::RenderPending)
     size_t host_stage_bytes = 0;
@@ -126,6 +129,8 @@ struct rt_ctx {
     int slices = -1;      // one-pass tree-walk launches: sample slices per pixel (FrameParams::slices; 0 off, -1 auto)
     int brute_refill = -1;   // one-lane brute-force kernels: free lanes a wave refills together (FrameParams::refill; -1 auto, 0 or 1 off, R)
     int denoise_lds = -1;    // the filter's pass at step 1 stages its tile in LDS (0 off, 1 on, -1 auto: kDenoiseLds)
+    int query_engine = 0;    // ray queries: 0 auto, 1 the plain form, 2 the persistent form (option "query_engine")
+    int query_grid = 0;      // ... at most this many blocks of the persistent form (0 auto; option "query_grid")
     bool accum_host = false;   // the open accumulation is rt_accum_begin's: every slot holds its rows of one frame
     // host wall times of the last calls (rt_debug_timings), ms: rt_set_scene's validation + packing and its
     // uploads (+ the per-triangle frame kernel), rt_set_env (upload + texel-sum kernel), rt_render's
@@ -388,7 +393,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.stream) (void)hipStreamSynchronize(d.stream);
         for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.brute_cbox, &d.brute_crow, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
                           &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum, &d.mark, &d.sel, &d.all,
-                          &d.dn, &d.dn_const, &d.guides, &d.dn_rgb, &d.dn_guides, &d.dn_out})
+                          &d.dn, &d.dn_const, &d.guides, &d.dn_rgb, &d.dn_guides, &d.dn_out, &d.q_counter, &d.q_rays, &d.q_out})
             release(*b);
         if (d.host_stage) (void)hipHostFree(d.host_stage);
         if (d.host_pick) (void)hipHostFree(d.host_pick);
@@ -545,6 +550,16 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
     if (!std::strcmp(key, "denoise_lds")) {
         if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "denoise_lds must be -1 (auto), 0 or 1");
         ctx->denoise_lds = (int)value;
+        return RT_OK;
+    }
+    if (!std::strcmp(key, "query_engine")) {
+        if (value < 0 || value > 2) return set_err(ctx, RT_ERR_ARG, "query_engine must be 0 (auto), 1 (plain) or 2 (persistent)");
+        ctx->query_engine = (int)value;
+        return RT_OK;
+    }
+    if (!std::strcmp(key, "query_grid")) {
+        if (value < 0 || value > (1 << 20)) return set_err(ctx, RT_ERR_ARG, "query_grid must be 0 (auto) or a block count");
+        ctx->query_grid = (int)value;
         return RT_OK;
     }
     if (!std::strcmp(key, "wdq")) {
@@ -1725,6 +1740,75 @@ int rt_gamma(rt_ctx* ctx, const float* in, float* out, int64_t n) {
     HIP_OR_RET(ctx, rt::launch_gamma((const float*)d.scratch_a.p, (float*)d.scratch_b.p, n, d.stream));
     HIP_OR_RET(ctx, hipMemcpyAsync(out, d.scratch_b.p, bytes, hipMemcpyDeviceToHost, d.stream));
     HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+namespace {
+// the argument and state checks the two query entry points share (n > 0 past them)
+int query_check(rt_ctx* ctx, const void* rays, int64_t n, int mode, const void* out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (n < 0 || n >= ((int64_t)1 << 31)) return set_err(ctx, RT_ERR_ARG, "ray count %lld out of range", (long long)n);
+    if (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_ANY) return set_err(ctx, RT_ERR_ARG, "no query mode %d", mode);
+    if (n > 0 && (!rays || !out)) return set_err(ctx, RT_ERR_ARG, "rays / out must not be NULL");
+    if (!ctx->have_scene) return set_err(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
+    if (ctx->traversal == RT_TRAVERSAL_FAST && !ctx->hs.fast_ok)
+        return set_err(ctx, RT_ERR_STATE, "FAST traversal unavailable for this scene");
+    return RT_OK;
+}
+
+// one slot's launch: ordered with the context's other launches, never waits
+int query_enqueue(rt_ctx* ctx, Device& d, const float* d_rays, int64_t n, int mode, rt_hit* d_out, hipStream_t s) {
+    HIP_OR_RET(ctx, ensure(d.q_counter, 256));
+    const bool wide = use_wide(ctx);
+    const rt::QueryOptions q{ctx->query_engine, ctx->query_grid,
+                             ctx->resume_min >= 0 ? ctx->resume_min : wide ? kResumeMinWide : kResumeMinBvh2,
+                             ctx->max_waves, ctx->block};
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_query(dev_scene(ctx, d), ctx->traversal, mode == RT_QUERY_ANY, (const float4*)d_rays,
+                                     (float4*)d_out, n, q, (unsigned int*)d.q_counter.p, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+}  // namespace
+
+int rt_trace_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, int mode, rt_hit* d_out,
+                    void* stream) {
+    const int st = query_check(ctx, d_rays, n, mode, d_out);
+    if (st) return st;
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    if (n == 0) return RT_OK;
+    const uintptr_t r0 = (uintptr_t)d_rays, o0 = (uintptr_t)d_out;
+    if ((r0 & 15) || (o0 & 15)) return set_err(ctx, RT_ERR_ARG, "d_rays and d_out must be 16-byte aligned");
+    if (r0 < o0 + (uintptr_t)n * sizeof(rt_hit) && o0 < r0 + (uintptr_t)n * 32)
+        return set_err(ctx, RT_ERR_ARG, "d_rays and d_out must not overlap");
+    Device& d = ctx->devs[device_index];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    return query_enqueue(ctx, d, d_rays, n, mode, d_out, (hipStream_t)stream);
+}
+
+int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out) {
+    const int st = query_check(ctx, rays, n, mode, out);
+    if (st) return st;
+    if (n == 0) return RT_OK;
+    // contiguous chunks over the slots; every slot is enqueued before any is waited for
+    const int64_t nd = (int64_t)ctx->devs.size();
+    for (int64_t k = 0; k < nd; ++k) {
+        const int64_t b = n * k / nd, m = n * (k + 1) / nd - b;
+        if (m <= 0) continue;
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, ensure(d.q_rays, (size_t)m * 32));
+        HIP_OR_RET(ctx, ensure(d.q_out, (size_t)m * sizeof(rt_hit)));
+        HIP_OR_RET(ctx, hipMemcpyAsync(d.q_rays.p, rays + 8 * b, (size_t)m * 32, hipMemcpyHostToDevice, d.stream));
+        const int qs = query_enqueue(ctx, d, (const float*)d.q_rays.p, m, mode, (rt_hit*)d.q_out.p, d.stream);
+        if (qs) return qs;
+        HIP_OR_RET(ctx, hipMemcpyAsync(out + b, d.q_out.p, (size_t)m * sizeof(rt_hit), hipMemcpyDeviceToHost, d.stream));
+    }
+    for (auto& d : ctx->devs) {
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    }
     return RT_OK;
 }
 

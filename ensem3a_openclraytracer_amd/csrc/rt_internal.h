@@ -305,6 +305,20 @@ KernelKey choose_kernel(const DevScene& sc, const FrameParams& fp, int traversal
 // waves per SIMD (0: no cap); 0 and *err set when the query fails or fn is null.  Each (device, fn, block, lds)
 // is queried once: the host query costs more than a launch.
 int64_t resident_blocks(const void* fn, int block, size_t lds, int max_waves, hipError_t* err);
+// Ray queries (rt_trace*, rt_api.h; kernels in rt_query.hip's translation unit): n rays (two float4 each: dir.xyz
+// origin.x | origin.yz tmax reserved) -> n results (k, tri bits, u, v), enqueued on `stream`.  The engine is the one
+// choose_kernel would take for the scene (REF, brute force, the 4-wide or the BVH2 walk), in the plain form (one
+// thread per ray, the whole stack in LDS) or the persistent one (a resident grid over the ray stream; counter:
+// one device word of the caller's, zeroed by the launch).
+struct QueryOptions {
+    int engine;       // option "query_engine": 0 auto, 1 plain, 2 persistent
+    int grid_cap;     // option "query_grid": at most this many blocks of the persistent form (0: the resident ones)
+    int resume_min;   // tree walks: new rays are handed out once this many of 64 lanes are free
+    int max_waves;    // option "waves"
+    int block;
+};
+hipError_t launch_query(const DevScene& sc, int traversal, int any, const float4* rays, float4* out, int64_t n,
+                        const QueryOptions& q, unsigned int* counter, hipStream_t stream);
 // test hooks
 // The process's last render launch (launch_pick) as its kernel got it: the refined key, FrameParams::team,
 // walk_team, slices and refill (0: every lane refilled at once), the grid and the dynamic LDS bytes

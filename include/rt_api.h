@@ -268,6 +268,42 @@ int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const f
                       int width, const rt_denoise_params* params, float* d_out, void* stream);
 int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb);
 
+/* Ray queries: closest-hit and any-hit batches of the caller's own rays through the uploaded scene (no
+ * counterpart in the reference).  Picking off the pixel grid, visibility between two points, ambient-occlusion or
+ * light-map baking, an integrator of the caller's own: the hits are the frame's hits, bit for bit.
+ *
+ * A ray is eight floats (32 bytes): dir.xyz, origin.xyz, tmax, reserved.  The first six are rt_debug_trace's
+ * layout; the direction is used as given, not normalised, as rayTrace uses it (MathLib.cl:234-288); reserved is
+ * never read.
+ *
+ * RT_QUERY_CLOSEST: the hit of the reference's rayTrace under the context's "traversal" option, exactly as a
+ * render sees it -- FAST: the closest triangle with the DFS-rank tie break; REF: the reference's DFS, the drops
+ * beyond "ref_stack" included -- restricted to k < lim, lim = fminf(tmax, 1000.0f): a NaN tmax means 1000, the
+ * reference's own horizon, and tmax <= 0 misses.  The restriction is a filter on the unrestricted closest hit:
+ * that hit when its k < lim, else a miss.
+ * Result: tri = the reference triangle index (the row of faceData), -1 for a miss; k = the distance, 1000.0f on a
+ * miss; u, v = Moller-Trumbore's barycentrics of that triangle, recomputed once per ray after the walk in the
+ * operation order of the reference's test with the IEEE 1.0f / a, 0 on a miss.
+ * RT_QUERY_ANY: tri >= 0 iff the closest-hit query would hit; tri, k, u, v then describe SOME triangle the ray
+ * really hits with k < lim, not necessarily the closest, and which one may differ between engines and options
+ * (the persistent tree walks end at the first accepted triangle; brute force, REF and the plain form return the
+ * closest).
+ *
+ *   rt_trace         host arrays, blocking: the rays are split in contiguous chunks over the device slots, every
+ *                    slot is enqueued before any is waited for.
+ *   rt_trace_device  DEVICE arrays on slot device_index, enqueued on the HIP stream `stream` (NULL = the default
+ *                    stream); never waits.  d_rays and d_out must be 16-byte aligned and must not overlap.
+ * A query reads the scene only: it needs no environment, leaves an open accumulation untouched and valid, and is
+ * ordered with the context's other launches and uploads as a render is.
+ * RT_ERR_STATE: no scene, or "traversal" is FAST and the scene has no FAST layout.  RT_ERR_ARG: n < 0, n >= 2^31,
+ * a mode that is none of the two, a device index out of range, NULL arrays with n > 0, misaligned or overlapping
+ * device arrays.  n == 0 is RT_OK and launches nothing. */
+typedef struct { float k; int32_t tri; float u, v; } rt_hit;   /* 16 bytes */
+enum rt_query_mode { RT_QUERY_CLOSEST = 0, RT_QUERY_ANY = 1 };
+int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out);
+int rt_trace_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, int mode, rt_hit* d_out,
+                    void* stream);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),

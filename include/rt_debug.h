@@ -30,7 +30,10 @@
  *   "stack_lds"    FAST stack entries per lane kept in LDS, deeper ones in HBM (0 auto)
  *   "sun_skip", "sun_any", "fixed_point", "sun_cache"  exact shortcuts of the shading loop (1 = on)
  *   "denoise_lds"  the denoise filter's pass at step 1 stages its tile and halo in LDS (0 taps from global
- *                  memory, -1 auto: 1) -- the same frame */
+ *                  memory, -1 auto: 1) -- the same frame
+ *   "query_engine" ray queries: 1 the plain form (one thread per ray, the whole stack in LDS), 2 the persistent
+ *                  form (a resident grid over the ray stream), 0 auto -- the same closest hits bit for bit
+ *   "query_grid"   ray queries, persistent form: at most this many blocks (0 auto: the resident ones) */
 
 #ifdef __cplusplus
 extern "C" {
