@@ -39,7 +39,8 @@ EXPORTED = (
     "rt_trace", "rt_trace_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
-    "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_slices", "rt_debug_last_slices",
+    "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_slices",
+    "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
@@ -48,7 +49,7 @@ EXPORTED = (
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
              "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout",
-             "rt_debug_brute_clusters", "rt_debug_brute_shell")
+             "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -188,6 +189,8 @@ def lib():
                                                _c_p, _i64, _c_p, _i64, _c_p]),
             "rt_debug_brute_shell": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32,
                                             _c_p, _i64, _c_p]),
+            "rt_debug_brute_near": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32,
+                                           _c_p, _i64, _c_p, _c_p]),
             "rt_debug_brute_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _c_p]),
             "rt_debug_last_slices": (_i32, []),
             "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
@@ -705,6 +708,30 @@ def brute_shell(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell:
                 rest=rec[SHELL_REC_FLOATS:].reshape(-1, 8).copy())
 
 
+NEAR_FLOOR = np.float32(0.0001) * (np.float32(1.0) - np.float32(2.0 ** -12))   # rt_layout.h kNearFloor
+
+
+def brute_near(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: int = -1, layout: int = RT_BVH_SAH):
+    """rt_debug_brute_near (include/rt_debug.h), on the host alone: ``(flags, floor, nfaces)`` -- flags[g] is True
+    where box g of brute_layout's array is near-safe (option "brute_near"), floor is the lower clamp the face tests
+    of the shell of brute_shell(cluster, shell) get (NEAR_FLOOR or 0.0) and nfaces that shell's faces (0: none)."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    H = host_lib()
+    info = np.zeros(2, np.int64)
+    floor = np.zeros(1, np.float32)
+    args = (ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size, ptr(b), b.size, int(layout),
+            int(cluster), int(shell))
+    st = H.rt_debug_brute_near(*args, None, 0, floor.ctypes.data, info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    flags = np.zeros(int(info[0]), np.int32)
+    st = H.rt_debug_brute_near(*args, flags.ctypes.data if flags.size else None, flags.size, floor.ctypes.data,
+                               info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    return flags.astype(bool), np.float32(floor[0]), int(info[1])
+
+
 def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: int = -1):
     """rt_debug_brute_slices (include/rt_debug.h): ``(on, K, tail)`` of the sample-slice rule for brute-force
     scenes, evaluated on the host alone."""
@@ -741,14 +768,15 @@ def last_refill():
 
 
 LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide", "brute", "ts", "acc",
-                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell")
+                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near")
 BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
 BRUTE_REFILL = 8
 
 
 def last_launch() -> dict:
     """rt_debug_last_launch (include/rt_debug.h): the kernel key of the last render launch and the team sizes,
-    slice word, refill threshold, grid and LDS bytes its kernel got and whether it walked a shell, by name
+    slice word, refill threshold, grid and LDS bytes its kernel got, whether it walked a shell and whether that
+    shell's face tests had a non-zero floor (option "brute_near"), by name
     (``LAUNCH_FIELDS``)."""
     out = np.zeros(len(LAUNCH_FIELDS), np.int32)
     st = lib().rt_debug_last_launch(out.ctypes.data)

@@ -107,6 +107,7 @@ struct rt_ctx {
     int brute_max = RT_BRUTE_MAX_DEFAULT;
     int brute_cluster = -1;  // brute force: clustered leaf boxes (0 off, 1 force, -1 auto; option "brute_cluster")
     int brute_shell = -1;    // ... and the shell among their single slots (0 off, 1 force, -1 auto; option "brute_shell")
+    int brute_near = -1;     // ... whose face tests take the packer's floor (0 off, -1 or 1 auto; option "brute_near")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
     int walk_team = 0;  // tree walk (BVH2 item steps): lanes per pixel walking each ray together, 0 = auto
@@ -270,6 +271,9 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.cluster_auto = ctx->brute_cluster < 0 ? 1 : 0;
     s.nsingle = ctx->hs.nsingle;
     s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
+    s.near_floor = s.shell && ctx->brute_near != 0 ? ctx->hs.shell_floor : 0.0f;
+    s.near_mask_lo = s.near_floor != 0.0f ? (uint32_t)ctx->hs.shell_mask : 0u;
+    s.near_mask_hi = s.near_floor != 0.0f ? (uint32_t)(ctx->hs.shell_mask >> 32) : 0u;
     s.stack_lds = std::min<int32_t>(s.depth > 0 ? s.depth : 1,
                                     ctx->stack_lds > 0 ? ctx->stack_lds : wide ? rt::kStackLdsWide : rt::kStackLds);
     s.stack_ovf = (int2*)d.stack_ovf.p;
@@ -412,6 +416,13 @@ int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
             return set_err(ctx, RT_ERR_ARG, "traversal must be 0 (fast) or 1 (ref)");
         ctx->traversal = (int)value;
         invalidate_accum(ctx);
+        return RT_OK;
+    }
+    if (!std::strcmp(key, "brute_near")) {
+        // no repack and no upload: the packer decides where the floor is safe whatever the option, and the floor
+        // reaches the kernels in DevScene, made for every launch (dev_scene); the frame is the same either way
+        if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "brute_near must be -1 (auto), 0 (off) or 1 (auto)");
+        ctx->brute_near = (int)value;
         return RT_OK;
     }
     if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max") || !std::strcmp(key, "brute_cluster") ||
@@ -1925,14 +1936,14 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 
 int rt_debug_last_slices(void) { return rt::last_launch().slices; }
 
-int rt_debug_last_launch(int32_t out[18]) {
+int rt_debug_last_launch(int32_t out[19]) {
     if (!out) return RT_ERR_ARG;
     const rt::LaunchNote n = rt::last_launch();
     const rt::KernelKey& k = n.key;
-    const int64_t v[18] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
+    const int64_t v[19] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
                            k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds,
-                           n.shell};
-    for (int i = 0; i < 18; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+                           n.shell, n.near};
+    for (int i = 0; i < 19; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
     return RT_OK;
 }
 

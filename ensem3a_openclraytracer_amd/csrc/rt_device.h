@@ -454,6 +454,13 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// the floor of box g of brute_box in the instrumented loops: kNearFloor for the faces of a shell that has it
+// (DevScene::near_mask_lo / _hi, boxes 0..63), else box_hit()'s 0.0f
+__device__ __forceinline__ float near_floor_of(const DevScene& S, int g) {
+    const uint32_t m = g < 32 ? S.near_mask_lo : S.near_mask_hi;
+    return g < 64 && ((m >> (g & 31)) & 1u) ? kNearFloor : 0.0f;
+}
+
 // a width of the lock-step walk's pieces, as a type (trace_brute_compact)
 template <int N> struct IntC { static constexpr int value = N; };
 static_assert(kBoxGroup == 1 || kBoxGroup == 2 || kBoxGroup == 4 || kBoxGroup == 8, "the lock-step tail is cut into powers of two");
@@ -557,7 +564,10 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             float tn, tx;
             slab(bx[2 * j].x, bx[2 * j].y, bx[2 * j].z, bx[2 * j].w, bx[2 * j + 1].x, bx[2 * j + 1].y, o, ix, iy, iz,
                  tn, tx);
-            pass[j] = box_hit(tn, tx, cull);
+            // the instrumented lock-step loop counts what the clustered product kernel queues: the shell's faces
+            // take its floor (DevScene::near_mask_lo / _hi: their boxes here)
+            if constexpr (COUNT && !CLU) pass[j] = fmaxf(tn, near_floor_of(S, g0 + j)) <= fminf(tx, cull);
+            else pass[j] = box_hit(tn, tx, cull);
         }
 #pragma unroll
         for (int j = 0; j < W; ++j) {
@@ -613,7 +623,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         if (S.shell) {
             const ConstF4 sh{cb.p + 4 * S.shell};
             const float4 h0 = sgpr4(sh[0]), h1 = sgpr4(sh[1]), fx = sgpr4(sh[2]), fy = sgpr4(sh[3]), fz = sgpr4(sh[4]);
-            const float cull = bk * CULL_MARGIN;
+            const float cull = bk * CULL_MARGIN, nearf = S.near_floor;
             const float x0 = (h0.x - o.x) * ix, x1 = (h0.y - o.x) * ix;
             const float y0 = (h0.z - o.y) * iy, y1 = (h0.w - o.y) * iy;
             const float z0 = (h1.x - o.z) * iz, z1 = (h1.y - o.z) * iz;
@@ -635,7 +645,12 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 const int a = f >> 1;
                 const float tn = fmaxf(fmaxf(a == 0 ? t[f] : mn[0], a == 1 ? t[f] : mn[1]), a == 2 ? t[f] : mn[2]);
                 const float tx = fminf(fminf(a == 0 ? t[f] : mx[0], a == 1 ? t[f] : mx[1]), a == 2 ? t[f] : mx[2]);
-                pass[f] = box_hit(tn, tx, cull);
+                // box_hit() with the shell's floor for its 0.0f (DevScene::near_floor, option "brute_near": kNearFloor
+                // where the packer found every face near-safe, else 0.0f itself): a pass with tx below the floor is
+                // one whose triangles return k <= 0.0001f.  The scalar is spilled to a lane and read
+                // back at each test, which the compiler sinks to its enqueue; folding the floor into two of the axis
+                // minima once per ray instead measured the same frame time and cost the adds' kernels a VGPR (r17)
+                pass[f] = fmaxf(tn, nearf) <= fminf(tx, cull);
             }
 #pragma unroll
             for (int f = 0; f < 6; ++f)
@@ -716,7 +731,8 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 const float4 b0 = boxrec[2 * g], b1 = boxrec[2 * g + 1];
                 float tn, tx;
                 slab(b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, o, ix, iy, iz, tn, tx);
-                pass = box_hit(tn, tx, bk * CULL_MARGIN);
+                if constexpr (COUNT) pass = fmaxf(tn, near_floor_of(S, g)) <= fminf(tx, bk * CULL_MARGIN);
+                else pass = box_hit(tn, tx, bk * CULL_MARGIN);
                 qa = __float_as_int(b1.z);
                 qb = __float_as_int(b1.w);
                 if (COUNT) { c.nodes += qb >= 0 ? 2 : 1; c.boxes++; }

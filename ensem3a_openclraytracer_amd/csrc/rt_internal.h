@@ -50,6 +50,7 @@ struct DevScene {
     // materials: the reference's 6 floats [type, r, g, b, roughness, ior] padded to kMatF = 8 (two float4)
     const float* mat;
     int32_t nmat;
+    uint32_t near_mask_hi;   // (see near_mask_lo)
     // IBL: the 2x2 texel sums the reference's lookup averages (ibl_sum_kernel), one word per clamped
     // integer coordinate (X, Y) in [0, ibl_w] x [0, ibl_h]: r | g << 10 | b << 20 (each <= 4 x 255)
     const uint32_t* ibl_sum;
@@ -63,6 +64,12 @@ struct DevScene {
     // (leaf box, a.p, e1, e2, triangle index); nbrute = 0 when the BVH path is used
     const float4* brute;
     int32_t nbrute;
+    // option "brute_near" for the instrumented kernels, which walk brute_box and no shell: bit g set (box g < 32 in
+    // near_mask_lo, 32 <= g < 64 in near_mask_hi above; boxes past 63 never) = box g is a face of the shell and
+    // near_floor is not 0, so rt_count_work* counts the triangle tests the product kernel queues.  (The three
+    // "brute_near" fields stand where the structure had padding, behind nbrute, nbox and nmat: no other field
+    // moves, and no kernel's arguments do.)
+    uint32_t near_mask_lo;
     // the distinct leaf boxes, 2 float4 each (lo.x hi.x lo.y hi.y | lo.z hi.z q0 q1): q0 (and q1 >= 0,
     // int bits) are the records whose leaf box it is.  Padded to whole groups of kBoxGroup (the lock-step
     // loop loads a group with one scalar wait) with a point at 1e30 that lists record 0 alone: a ray
@@ -71,6 +78,10 @@ struct DevScene {
     // (scene_pack.cpp pad_box; tests/test_malformed_inputs.py checks every slot)
     const float4* brute_box;
     int32_t nbox;
+    // the lower clamp of the shell's face tests (option "brute_near"): rt::kNearFloor where the
+    // packer found every face near-safe (HostScene::shell_floor) and the option is not 0, else 0.0f -- box_hit()'s
+    // own clamp
+    float near_floor;
     // the same boxes clustered (scene_pack.cpp build_clusters, option "brute_cluster"; ncluster = 0: not
     // clustered): brute_cbox = ncslot slots of brute_box's form, the single boxes padded to nsingle4 (whole
     // groups of kBoxGroup), then kClusterSlots slots per cluster (padded; every padding slot lists record 0
@@ -328,6 +339,7 @@ struct LaunchNote {
     int64_t grid;
     size_t lds;
     int shell;   // the kernel walks the scene's shell (the clustered loop, DevScene::shell != 0)
+    int near;    // ... with a non-zero floor in its face tests (DevScene::near_floor != 0)
 };
 void note_launch(const LaunchNote& n);
 LaunchNote last_launch();

@@ -1375,7 +1375,8 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     const LaunchConst* lc = nullptr;
     if (e == hipSuccess) e = setup_work_block(f, d_work, stream, &lc);
     if (e != hipSuccess) return e;
-    note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, (k.brute & 3) == 3 && sc.shell != 0});
+    const int shell = (k.brute & 3) == 3 && sc.shell != 0;
+    note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f});
     DevScene a0 = sc;
     void* args[] = {&a0, &f, &d_out, &d_counts, &d_work, &lc};
     return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);

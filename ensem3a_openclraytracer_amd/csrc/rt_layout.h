@@ -47,6 +47,16 @@ constexpr int kClusterLockNum = 4;
 // for two faces, at most 53 against 69 for three
 constexpr int kShellRecF = 20;
 constexpr int kShellMinFaces = 3;
+// The floor of the shell's face tests (option "brute_near", DevScene::near_floor; DESIGN.md 4.2 has the proof).  A
+// ray that starts on a wall passes that wall's flat box at a plane distance t of 0 to a few 1e-7, and the wall's
+// triangles then return k = t up to rounding, which the k > 0.0001f of the hit condition throws away.  A face test
+// whose lower clamp is this floor instead of 0 drops such passes before they are queued.  It stays 2^-12 below the
+// 0.0001f of the hit condition; for a box the packer found near-safe (scene_pack.cpp near_safe: flat on one axis,
+// its records in that plane, cancellation factor kappa <= kNearKappa, components within 2^+-kNearExp) k exceeds t
+// by less than 2^-13.9 of it, so every dropped pair is one Moller-Trumbore rejects.  0.0f: today's test
+constexpr float kNearFloor = 0.0001f * (1.0f - 0x1p-12f);
+constexpr double kNearKappa = 256.0;   // (|e1b e2c| + |e1c e2b|) / |e1b e2c - e1c e2b| of a near-safe record, at most
+constexpr int kNearExp = 40;           // its non-zero components, and the box's bounds, lie in [2^-40, 2^40]
 #ifndef RT_BRUTE_MAX_DEFAULT
 #define RT_BRUTE_MAX_DEFAULT 64   // FAST tests every triangle of scenes up to this size (rt_set_option "brute_max")
 #endif

@@ -502,6 +502,44 @@ void build_clusters(HostScene& hs, int mode) {
     hs.nsingle = (int32_t)singles.size();
 }
 
+// Near-safe boxes (option "brute_near", HostScene::brute_near; the proof is DESIGN.md 4.2): slot b (8 floats of
+// brute_box's form) is flat on exactly one axis a at a finite h, a proper finite range on the other two, and each
+// of its one or two records, as the kernel reads it from hs.brute, lies in that plane -- p0[a] == h, e1[a] and
+// e2[a] zero -- with an in-plane cross product N = e1[b] e2[c] - e1[c] e2[b] that is not zero and cancels by at
+// most kNearKappa, every non-zero component and bound within 2^+-kNearExp.  Then Moller-Trumbore's k on such a
+// record is the box's own plane distance to a relative 2^-13.9, whatever the ray: a pass closer than kNearFloor is
+// no hit.  Evaluated in double, in which the products of two floats and the comparisons below are exact.
+bool near_safe(const HostScene& hs, const float* b) {
+    int nf = 0, ax = -1;
+    const double lim_lo = std::ldexp(1.0, -rt::kNearExp), lim_hi = std::ldexp(1.0, rt::kNearExp);
+    auto in_range = [&](double v) { return v == 0.0 || (std::fabs(v) >= lim_lo && std::fabs(v) <= lim_hi); };
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(b[2 * a]) || !std::isfinite(b[2 * a + 1])) return false;
+        if (!in_range(b[2 * a]) || !in_range(b[2 * a + 1])) return false;
+        if (b[2 * a] == b[2 * a + 1]) { ++nf; ax = a; }
+        else if (!(b[2 * a] < b[2 * a + 1])) return false;
+    }
+    if (nf != 1) return false;
+    const double h = b[2 * ax];
+    const int u = (ax + 1) % 3, v = (ax + 2) % 3;
+    int32_t q[2];
+    std::memcpy(q, b + 6, 8);
+    for (int j = 0; j < 2; ++j) {
+        if (j == 1 && q[1] < 0) break;
+        if (q[j] < 0 || q[j] >= hs.nbrute) return false;
+        const float* r = hs.brute.data() + 16 * (size_t)q[j];
+        const float *p0 = r + 6, *e1 = r + 9, *e2 = r + 12;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p0[k]) || !std::isfinite(e1[k]) || !std::isfinite(e2[k]) || !in_range(p0[k]) ||
+                !in_range(e1[k]) || !in_range(e2[k]))
+                return false;
+        if ((double)p0[ax] != h || e1[ax] != 0.0f || e2[ax] != 0.0f) return false;
+        const double t1 = (double)e1[u] * e2[v], t2 = (double)e1[v] * e2[u], N = t1 - t2;
+        if (N == 0.0 || !((std::fabs(t1) + std::fabs(t2)) <= rt::kNearKappa * std::fabs(N))) return false;
+    }
+    return true;
+}
+
 // The shell of a clustered scene (HostScene::brute_shell; option "brute_shell", mode 0 off, < 0 auto, > 0 force):
 // a box S with lo < hi, finite, on every axis, and the single slots that are faces of it -- a slot is a face when
 // its box is flat on one axis at S's lower or upper bound there and equals S's range on the other two, every
@@ -519,6 +557,8 @@ void build_shell(HostScene& hs, int mode) {
     hs.brute_shell.clear();
     hs.nshell = 0;
     hs.nrest = 0;
+    hs.shell_floor = 0.0f;
+    hs.shell_mask = 0;
     if (mode == 0 || hs.ncluster == 0) return;
     const int32_t n = hs.nsingle;
     auto bits = [](float f) {
@@ -616,6 +656,14 @@ void build_shell(HostScene& hs, int mode) {
         }
     hs.nshell = (int32_t)best_slots.size();
     hs.nrest = nrest;
+    // one floor for all the face tests (option "brute_near"): only when every face present is near-safe
+    bool near = true;
+    for (int32_t s : best_slots) near = near && near_safe(hs, box(s));
+    hs.shell_floor = near ? rt::kNearFloor : 0.0f;
+    // the faces' boxes in brute_box, by their first record (a record belongs to one box)
+    for (int32_t s : best_slots)
+        for (int32_t g = 0; g < hs.nbox && g < 64; ++g)
+            if (as_i32(hs.brute_box[8 * (size_t)g + 6]) == as_i32(box(s)[6])) hs.shell_mask |= 1ull << g;
 }
 
 // Pack the FAST layout from the reference export.  Returns false (with
@@ -706,6 +754,9 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
     hs.brute_shell.clear();
     hs.nshell = 0;
     hs.nrest = 0;
+    hs.brute_near.clear();
+    hs.shell_floor = 0.0f;
+    hs.shell_mask = 0;
     if ((int64_t)leaves.size() <= (int64_t)brute_max) {
         std::vector<int32_t> by_rank(leaves.size());
         for (int32_t n : leaves) by_rank[rank[T[n]]] = n;
@@ -758,6 +809,8 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
                 pad_box(b);
             }
         }
+        hs.brute_near.assign((size_t)hs.nbox, 0);
+        for (int32_t g = 0; g < hs.nbox; ++g) hs.brute_near[g] = near_safe(hs, hs.brute_box.data() + 8 * (size_t)g);
         build_clusters(hs, cluster);
         build_shell(hs, shell);
     }
@@ -811,8 +864,8 @@ void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, in
         hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0;
     }
     if (!hs.fast_ok) { hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0; }
-    if (hs.nbrute == 0) { hs.brute_cbox.clear(); hs.brute_crow.clear(); hs.ncluster = 0; hs.nsingle = 0; }
-    if (hs.ncluster == 0) { hs.brute_shell.clear(); hs.nshell = 0; hs.nrest = 0; }
+    if (hs.nbrute == 0) { hs.brute_cbox.clear(); hs.brute_crow.clear(); hs.ncluster = 0; hs.nsingle = 0; hs.brute_near.clear(); }
+    if (hs.ncluster == 0) { hs.brute_shell.clear(); hs.nshell = 0; hs.nrest = 0; hs.shell_floor = 0.0f; hs.shell_mask = 0; }
     if (!hs.fast_ok || hs.wdepth > 64) { hs.wnodes.clear(); hs.wleaves.clear(); hs.nwnodes = 0; hs.wdepth = 1; }
     // render kernels keep kStackLds entries in LDS and spill deeper ones to HBM; the single-ray
     // debug kernel keeps the whole stack in LDS (int2 entries, 128 lanes): depth <= 64
@@ -1047,5 +1100,35 @@ extern "C" int rt_debug_brute_shell(const float* vp, int64_t nvp, const float* v
     info[2] = (int64_t)hs.brute_shell.size();
     const int64_t n = std::min<int64_t>(cap, info[2]);
     if (n > 0) std::memcpy(rec, hs.brute_shell.data(), (size_t)n * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_brute_near(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                   int layout, int cluster, int shell, int32_t* flags, int64_t cap, float* floor,
+                                   int64_t info[2]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (cluster < -1 || cluster > 1 || shell < -1 || shell > 1) {
+        g_check_error = "brute_cluster and brute_shell must be -1 (auto), 0 (off) or 1 (force)";
+        return RT_ERR_ARG;
+    }
+    if (!info || !floor || cap < 0 || (cap > 0 && !flags)) {
+        g_check_error = "null info or floor, or a capacity without an array";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[0] = (int64_t)hs.brute_near.size();
+    info[1] = hs.nshell;
+    *floor = hs.shell_floor;
+    const int64_t n = std::min<int64_t>(cap, info[0]);
+    for (int64_t g = 0; g < n; ++g) flags[g] = hs.brute_near[(size_t)g];
     return RT_OK;
 }

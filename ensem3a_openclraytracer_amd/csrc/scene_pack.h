@@ -37,6 +37,12 @@ struct HostScene {
     // are no face, 8 floats per slot in brute_cbox order, padded to whole groups
     std::vector<float> brute_shell;
     int32_t nshell = 0, nrest = 0;       // faces of the shell; single slots outside it
+    // option "brute_near" (scene_pack.cpp near_safe): 1 for each of the nbox boxes of brute_box that
+    // is near-safe -- a ray that passes it closer than rt::kNearFloor cannot hit its records -- and the floor of the
+    // shell's face tests: rt::kNearFloor when the shell's every face is such a box, else 0
+    std::vector<uint8_t> brute_near;
+    float shell_floor = 0.0f;
+    uint64_t shell_mask = 0;   // bit g: box g of brute_box (g < 64) is a face of the shell (DevScene::near_mask_lo / _hi)
     int32_t nnodes = 0, root_ref = 0, ntri = 0, nmat = 0, nbvh9 = 0, depth = 1;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     bool fast_ok = false;

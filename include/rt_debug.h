@@ -17,6 +17,10 @@
  *                  rays' (ray, box) tests compacted (0 off, 1 every SAH subtree of 2..8 boxes, -1 auto by cost)
  *   "brute_shell"  clustered brute force: the single boxes that are faces of one box (a room's walls) are tested
  *                  from its six plane distances, computed once per ray (0 off, 1 from two faces, -1 auto from three)
+ *   "brute_near"   clustered brute force with a shell: the faces' tests take kNearFloor (rt_layout.h, just under the
+ *                  hit condition's 1e-4) as their lower clamp instead of 0 where the packer found every face
+ *                  near-safe, so a ray is not tested against the triangles of the wall it starts on (0 off: clamp
+ *                  0, -1 auto; 1 means auto: there is no way to force an unsafe floor)
  *   "brute_refill" brute force, one lane per pixel: a wave hands out jobs once this many lanes are free, 2..64
  *                  (0 or 1 every free lane at once, -1 auto: 4 on tiles of >= 1.5 pixels per resident lane)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
@@ -155,6 +159,15 @@ int rt_debug_brute_shell(const float* V_p, int64_t n_vp, const float* V_n, int64
                          int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
                          int layout, int cluster, int shell, float* rec, int64_t cap, int64_t info[3]);
 
+/* Host-only (no device): which boxes of rt_debug_brute_layout's array are near-safe (option "brute_near": flat on
+ * one axis, their records in that plane, well conditioned; a ray that passes such a box closer than kNearFloor
+ * cannot hit its records), and the floor the shell of rt_debug_brute_shell(cluster, shell) gets.  info[0] = distinct
+ * leaf boxes, info[1] = faces of the shell (0: none); the first min(cap, info[0]) flags (1 / 0) are copied to flags
+ * (NULL when cap is 0); *floor = kNearFloor when there is a shell and its every face is near-safe, else 0. */
+int rt_debug_brute_near(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                        int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                        int layout, int cluster, int shell, int32_t* flags, int64_t cap, float* floor, int64_t info[2]);
+
 /* No device call: the rule for sample slices on a brute-force scene (option "slices" = option: -1 auto, 0 off,
  * K) for a launch over a tile of nloc pixels on a device that keeps `lanes` lanes of the kernel resident, which
  * brings every pixel to spp samples; accum_base >= 0: an add of a progressive accumulation that has accum_base of
@@ -173,8 +186,9 @@ int rt_debug_last_slices(void);
  * ts (lanes per pixel of the tree walk), acc (0 one-shot, 1 an add, 2 a listed add); out[11..14] = the brute-force
  * team size, the walk's team size, the slice word (rt_debug_last_slices) and R (rt_debug_last_refill) of its
  * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block; out[17] = 1 when the kernel
- * walked a shell (option "brute_shell": the clustered loop on a scene that has one), else 0. */
-int rt_debug_last_launch(int32_t out[18]);
+ * walked a shell (option "brute_shell": the clustered loop on a scene that has one), else 0; out[18] = 1 when it
+ * walked that shell with a non-zero floor (option "brute_near"), else 0. */
+int rt_debug_last_launch(int32_t out[19]);
 
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
