@@ -43,9 +43,25 @@ namespace {
 
 thread_local std::string g_thread_error;
 
+// A device allocation that frees itself: whoever lets one go (grow, release, ~Device) has the device selected
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
 };
 
 struct Device {
@@ -92,6 +108,19 @@ struct Device {
     hipEvent_t done = nullptr;
     hipStream_t last = nullptr;
     bool pending = false;
+
+    Device() = default;
+    Device(const Device&) = delete;
+    Device& operator=(const Device&) = delete;
+    // rt_destroy has waited for the slot's work.  The device stays selected while the members go: every DevBuf
+    // above frees itself, so a buffer added to this struct needs no line anywhere else
+    ~Device() {
+        (void)hipSetDevice(id);
+        if (host_stage) (void)hipHostFree(host_stage);
+        if (host_pick) (void)hipHostFree(host_pick);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (done) (void)hipEventDestroy(done);
+    }
 };
 
 }  // namespace
@@ -160,24 +189,31 @@ int set_err(rt_ctx* ctx, int code, const char* fmt, ...) {
             return set_err((ctx), RT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));           \
     } while (0)
 
-hipError_t ensure(DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return hipSuccess;
-    if (b.p) {
-        hipError_t e = hipFree(b.p);
-        if (e != hipSuccess) return e;
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    if (bytes == 0) return hipSuccess;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e == hipSuccess) b.bytes = bytes;
+// The one way a buffer of a slot gets its size (at least 16 bytes: never a NULL pointer).  Growing frees the old
+// allocation from the host, and the slot's last launch, on whatever stream, may still read or write it: a slot with
+// a launch pending waits for it first.  Only a buffer that grows pays for that, next to its hipFree and hipMalloc;
+// one that is large enough returns at the first line.
+hipError_t grow(Device& d, DevBuf& b, size_t bytes) {
+    bytes = std::max<size_t>(bytes, 16);
+    if (b.p && b.bytes >= bytes) return hipSuccess;
+    hipError_t e = d.pending ? hipEventSynchronize(d.done) : hipSuccess;
+    if (e != hipSuccess) return e;
+    if (b.p && (e = hipFree(b.p)) != hipSuccess) return e;
+    b.p = nullptr;
+    b.bytes = 0;
+    if ((e = hipMalloc(&b.p, bytes)) == hipSuccess) b.bytes = bytes;
     return e;
 }
 
-void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
+// ... and the pinned stage of the host forms' read-back (no copy into it is in flight between two calls)
+hipError_t grow_stage(Device& d, size_t bytes) {
+    if (d.host_stage_bytes >= bytes) return hipSuccess;
+    hipError_t e = d.host_stage ? hipHostFree(d.host_stage) : hipSuccess;
+    if (e != hipSuccess) return e;
+    d.host_stage = nullptr;
+    d.host_stage_bytes = 0;
+    if ((e = hipHostMalloc((void**)&d.host_stage, bytes, hipHostMallocDefault)) == hipSuccess) d.host_stage_bytes = bytes;
+    return e;
 }
 
 }  // namespace
@@ -190,7 +226,7 @@ constexpr int kStackLdsMin = 8;
 hipError_t ensure_stack_ovf(Device& d, const HostScene& hs) {
     const int64_t extra = (int64_t)std::max(hs.depth, hs.wdepth) - kStackLdsMin;
     if (extra <= 0) return hipSuccess;
-    return ensure(d.stack_ovf, (size_t)std::max(d.cus, 1) * rt::kMaxLanesPerCu * (size_t)extra * sizeof(int2));
+    return grow(d, d.stack_ovf, (size_t)std::max(d.cus, 1) * rt::kMaxLanesPerCu * (size_t)extra * sizeof(int2));
 }
 
 hipError_t order_after_last(Device& d, hipStream_t s) {
@@ -205,20 +241,38 @@ hipError_t mark_launch(Device& d, hipStream_t s) {
 }
 
 template <typename T>
-hipError_t upload(DevBuf& b, const std::vector<T>& v, hipStream_t s) {
+hipError_t upload(Device& d, DevBuf& b, const std::vector<T>& v) {
     const size_t bytes = v.size() * sizeof(T);
-    hipError_t e = ensure(b, bytes > 0 ? bytes : 16);
+    hipError_t e = grow(d, b, bytes);
     if (e != hipSuccess || bytes == 0) return e;
-    return hipMemcpyAsync(b.p, v.data(), bytes, hipMemcpyHostToDevice, s);
+    return hipMemcpyAsync(b.p, v.data(), bytes, hipMemcpyHostToDevice, d.stream);
 }
 
 // DevScene::brute_cbox: the clustered slots, then the shell's record and slots (DevScene::shell)
 hipError_t upload_cbox(Device& d, const HostScene& hs) {
-    if (hs.brute_shell.empty()) return upload(d.brute_cbox, hs.brute_cbox, d.stream);
+    if (hs.brute_shell.empty()) return upload(d, d.brute_cbox, hs.brute_cbox);
     std::vector<float> v(hs.brute_cbox);
     v.insert(v.end(), hs.brute_shell.begin(), hs.brute_shell.end());
-    const hipError_t e = upload(d.brute_cbox, v, d.stream);
+    const hipError_t e = upload(d, d.brute_cbox, v);
     return e != hipSuccess ? e : hipStreamSynchronize(d.stream);   // v leaves scope: the copy is done first
+}
+
+// The FAST layout of a packed scene on one slot, on its stream (rt_set_scene, and the options that pack the scene
+// again): uploads are ordered after the slot's last launch, and a buffer that has to grow waits for it (grow)
+int upload_fast(rt_ctx* ctx, Device& d, const HostScene& hs) {
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    HIP_OR_RET(ctx, upload(d, d.nodes, hs.nodes));
+    HIP_OR_RET(ctx, upload(d, d.wnodes, hs.wnodes));
+    HIP_OR_RET(ctx, upload(d, d.wleaves, hs.wleaves));
+    HIP_OR_RET(ctx, upload(d, d.brute, hs.brute));
+    HIP_OR_RET(ctx, upload(d, d.brute_box, hs.brute_box));
+    HIP_OR_RET(ctx, upload_cbox(d, hs));
+    HIP_OR_RET(ctx, upload(d, d.brute_crow, hs.brute_crow));
+    HIP_OR_RET(ctx, upload(d, d.tri_geo, hs.tri_geo));
+    HIP_OR_RET(ctx, upload(d, d.tri_fast, hs.tri_fast));
+    HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
+    return RT_OK;
 }
 
 int effective_traversal(const rt_ctx* ctx) {
@@ -230,6 +284,11 @@ int effective_traversal(const rt_ctx* ctx) {
 bool use_wide(const rt_ctx* ctx) {
     if (ctx->hs.wnodes.empty() || ctx->bvh_width == 2) return false;
     return ctx->bvh_width == 4 || (size_t)ctx->hs.nnodes * 16 * rt::kNodeF4 > rt::kWideMinBytes;
+}
+
+// the resumable walk's threshold where "resume_min" leaves it to the layout
+int resume_min_of(const rt_ctx* ctx) {
+    return ctx->resume_min >= 0 ? ctx->resume_min : use_wide(ctx) ? kResumeMinWide : kResumeMinBvh2;
 }
 
 rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
@@ -280,8 +339,8 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     return s;
 }
 
-int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, int spp, int row0, int row_step,
-                rt::FrameParams* fp) {
+int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, int spp, int max_bounce, int row0,
+                int row_step, rt::FrameParams* fp) {
     if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
     if (!ctx->have_scene) return set_err(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
     if (!ctx->have_env) return set_err(ctx, RT_ERR_STATE, "rt_set_env has not been called");
@@ -291,16 +350,18 @@ int check_frame(rt_ctx* ctx, const float* cam, const float* env, int64_t npix, i
     if (npix <= 0 || npix > 0x7fffffff) return set_err(ctx, RT_ERR_ARG, "pixel count %lld out of range", (long long)npix);
     if (spp < 0) return set_err(ctx, RT_ERR_ARG, "spp must be >= 0");
     if (row0 < 0 || row_step <= 0) return set_err(ctx, RT_ERR_ARG, "bad row tiling (%d, %d)", row0, row_step);
+    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
     std::memcpy(fp->cam, cam, sizeof fp->cam);
     std::memcpy(fp->env, env, sizeof fp->env);
     fp->width = (int32_t)cam[6];
     fp->npix = npix;
     fp->spp = spp;
+    fp->max_bounce = max_bounce;
     fp->row0 = row0;
     fp->row_step = row_step;
     fp->nloc = rt_tile_rows(npix, fp->width, row0, row_step) * fp->width;
     fp->log_pixel = -1;
-    fp->resume_min = ctx->resume_min >= 0 ? ctx->resume_min : use_wide(ctx) ? kResumeMinWide : kResumeMinBvh2;
+    fp->resume_min = resume_min_of(ctx);
     fp->step = ctx->step;
     fp->sun_skip = (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite) ? 1 : 0;
     fp->sun_any = (ctx->sun_any && !ctx->hs.has_glass) ? 1 : 0;
@@ -345,6 +406,108 @@ void invalidate_accum(rt_ctx* ctx) {
     }
 }
 
+// the slot an entry point names (`what`: how that entry point spells the argument in its message)
+int slot_of(rt_ctx* ctx, int device_index, Device** d, const char* what = "device index") {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+        return set_err(ctx, RT_ERR_ARG, "%s %d out of range", what, device_index);
+    *d = &ctx->devs[device_index];
+    return RT_OK;
+}
+
+// The options that pack the scene again ("bvh", "brute_max", "brute_cluster", "brute_shell"): the FAST layout of
+// the current scene from the values as they are now, on every slot.  Without a scene there is nothing to do.
+int repack_scene(rt_ctx* ctx) {
+    if (!ctx->have_scene) return RT_OK;
+    HostScene& hs = ctx->hs;
+    std::string why;
+    rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster,
+                     ctx->brute_shell, why);
+    for (auto& d : ctx->devs) {
+        const int st = upload_fast(ctx, d, hs);
+        if (st) return st;
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    }
+    if (!hs.fast_ok) ctx->err = "FAST traversal unavailable (" + why + "); REF traversal will be used";
+    return RT_OK;
+}
+
+// ---- rt_set_option: one row per key ----
+// What a key accepts: a closed range, 0 or a closed range, or a short set
+struct Accepts {
+    enum Kind { kRange, kZeroOrRange, kSet } kind;
+    int n;
+    int64_t v[5];   // kRange, kZeroOrRange: v[0]..v[1]; kSet: the n members
+    bool operator()(int64_t x) const {
+        if (kind == kSet) return std::find(v, v + n, x) != v + n;
+        return (kind == kZeroOrRange && x == 0) || (x >= v[0] && x <= v[1]);
+    }
+};
+Accepts range(int64_t lo, int64_t hi) { return {Accepts::kRange, 2, {lo, hi}}; }
+Accepts zero_or(int64_t lo, int64_t hi) { return {Accepts::kZeroOrRange, 2, {lo, hi}}; }
+Accepts one_of(std::initializer_list<int64_t> members) {
+    Accepts a{Accepts::kSet, (int)members.size(), {}};
+    std::copy(members.begin(), members.end(), a.v);
+    return a;
+}
+
+enum class Effect { kNone, kInvalidate, kRepack };   // after the store: nothing, invalidate_accum, repack_scene
+
+struct Option {
+    const char* key;
+    int rt_ctx::*field;   // (the defaults are rt_ctx's member initialisers)
+    Accepts accepts;
+    std::string message;  // of a refused value
+    Effect effect;
+};
+
+std::string bounds_message(const char* fmt, int a, int b = 0) {
+    char buf[128];
+    snprintf(buf, sizeof buf, fmt, a, b);
+    return buf;
+}
+
+const std::vector<Option>& options() {
+    constexpr Effect none = Effect::kNone, invalidate = Effect::kInvalidate, repack = Effect::kRepack;
+    static const std::vector<Option> table = {
+        {"traversal", &rt_ctx::traversal, range(RT_TRAVERSAL_FAST, RT_TRAVERSAL_REF), "traversal must be 0 (fast) or 1 (ref)", invalidate},
+        // no repack and no upload: the packer decides where the floor is safe whatever the option, and the floor
+        // reaches the kernels in DevScene, made for every launch (dev_scene); the frame is the same either way
+        {"brute_near", &rt_ctx::brute_near, range(-1, 1), "brute_near must be -1 (auto), 0 (off) or 1 (auto)", none},
+        {"bvh", &rt_ctx::bvh_layout, range(RT_BVH_REFERENCE, RT_BVH_SAH), "bvh must be 0 (reference tree) or 1 (sah)", repack},
+        {"brute_cluster", &rt_ctx::brute_cluster, range(-1, 1), "brute_cluster must be -1 (auto), 0 (off) or 1 (force)", repack},
+        {"brute_shell", &rt_ctx::brute_shell, range(-1, 1), "brute_shell must be -1 (auto), 0 (off) or 1 (force)", repack},
+        {"brute_max", &rt_ctx::brute_max, range(0, 4096), "brute_max must be in 0..4096", repack},
+        {"resume_min", &rt_ctx::resume_min, range(-1, 64), "resume_min must be -1 (auto) or 0..64", none},
+        {"team", &rt_ctx::team, one_of({0, 1, 2, 4, 8}), "team must be 0 (auto), 1, 2, 4 or 8", none},
+        {"walk_team", &rt_ctx::walk_team, one_of({0, 1, 2, 4, 8}), "walk_team must be 0 (auto), 1, 2, 4 or 8", none},
+        {"sun_any", &rt_ctx::sun_any, range(0, 1), "sun_any must be 0 or 1", none},
+        {"sun_skip", &rt_ctx::sun_skip, range(0, 1), "sun_skip must be 0 or 1", none},
+        {"step", &rt_ctx::step, range(0, 2), "step must be 0 (auto), 1 (item) or 2 (round)", none},
+        {"waves", &rt_ctx::max_waves, range(0, 8), "waves must be in 0..8", none},
+        {"pilot", &rt_ctx::pilot, range(-1, 1 << 20), "pilot must be -1 (auto), 0 (off) or a sample count", none},
+        {"pilot_chunk", &rt_ctx::pilot_chunk, range(0, 4096), "pilot_chunk must be in 0..4096 (0 = auto)", none},
+        {"pilot_levels", &rt_ctx::pilot_levels, zero_or(2, 256), "pilot_levels must be 0 (auto) or 2..256", none},
+        {"stack_lds", &rt_ctx::stack_lds, zero_or(kStackLdsMin, rt::kStackLds),
+         bounds_message("stack_lds must be 0 (auto) or %d..%d", kStackLdsMin, rt::kStackLds), none},
+        {"sun_cache", &rt_ctx::sun_cache, range(0, 1), "sun_cache must be 0 or 1", none},
+        {"fixed_point", &rt_ctx::fixed_point, range(0, 1), "fixed_point must be 0 or 1", none},
+        {"bvh_width", &rt_ctx::bvh_width, one_of({0, 2, 4}), "bvh_width must be 0 (auto), 2 or 4", none},
+        {"ref_stack", &rt_ctx::ref_stack, range(20, 64), "ref_stack must be in 20..64 (20 = the reference's)", invalidate},
+        {"slices", &rt_ctx::slices, range(-1, 16), "slices must be -1 (auto), 0 (off) or 1..16", none},
+        {"brute_refill", &rt_ctx::brute_refill, range(-1, rt::kRefillMax),
+         bounds_message("brute_refill must be -1 (auto), 0 or 1 (off) or 2..%d", rt::kRefillMax), none},
+        {"denoise_lds", &rt_ctx::denoise_lds, range(-1, 1), "denoise_lds must be -1 (auto), 0 or 1", none},
+        {"query_engine", &rt_ctx::query_engine, range(0, 2), "query_engine must be 0 (auto), 1 (plain) or 2 (persistent)", none},
+        {"query_grid", &rt_ctx::query_grid, range(0, 1 << 20), "query_grid must be 0 (auto) or a block count", none},
+        {"wdq", &rt_ctx::wdq, range(0, 1), "wdq must be 0 or 1", none},
+        {"handout", &rt_ctx::handout, range(-1, 1), "handout must be -1 (auto), 0 or 1", none},
+        {"spec", &rt_ctx::spec, one_of({-1, 0, 2, 4, 8}), "spec must be -1 (auto), 0 (off), 2, 4 or 8", none},
+        {"block", &rt_ctx::block, one_of({64, 128, 256}), "block must be 64/128/256", none},
+    };
+    return table;
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,7 +532,7 @@ int rt_create(int n_devices, const int* device_ids, rt_ctx** out) {
         return set_err(nullptr, RT_ERR_ARG, "requested %d devices, %d available", n_devices, avail);
     if (n_devices > 64) return set_err(nullptr, RT_ERR_ARG, "at most 64 device slots, got %d", n_devices);
     rt_ctx* ctx = new rt_ctx();
-    ctx->devs.resize(n_devices);
+    ctx->devs = std::vector<Device>(n_devices);
     for (int i = 0; i < n_devices; ++i) {
         const int id = device_ids ? device_ids[i] : i;
         if (id < 0 || id >= avail) {
@@ -391,18 +554,10 @@ int rt_create(int n_devices, const int* device_ids, rt_ctx** out) {
 
 void rt_destroy(rt_ctx* ctx) {
     if (!ctx) return;
-    for (auto& d : ctx->devs) {
+    for (auto& d : ctx->devs) {   // every slot's work ends before ~Device lets go of what it uses
         if (hipSetDevice(d.id) != hipSuccess) continue;
         if (d.pending) (void)hipEventSynchronize(d.done);
         if (d.stream) (void)hipStreamSynchronize(d.stream);
-        for (DevBuf* b : {&d.stack_ovf, &d.nodes, &d.wnodes, &d.wleaves, &d.tri_fast, &d.brute, &d.brute_box, &d.brute_cbox, &d.brute_crow, &d.bvh9, &d.tri_geo, &d.tri_shade, &d.tri_frame, &d.mat, &d.ibl, &d.ibl_sum, &d.out,
-                          &d.out8, &d.counts, &d.work, &d.scratch_a, &d.scratch_b, &d.pilot, &d.spec, &d.slice, &d.accum, &d.mark, &d.sel, &d.all,
-                          &d.dn, &d.dn_const, &d.guides, &d.dn_rgb, &d.dn_guides, &d.dn_out, &d.q_counter, &d.q_rays, &d.q_out})
-            release(*b);
-        if (d.host_stage) (void)hipHostFree(d.host_stage);
-        if (d.host_pick) (void)hipHostFree(d.host_pick);
-        if (d.stream) (void)hipStreamDestroy(d.stream);
-        if (d.done) (void)hipEventDestroy(d.done);
     }
     delete ctx;
 }
@@ -411,188 +566,12 @@ const char* rt_last_error(rt_ctx* ctx) { return ctx ? ctx->err.c_str() : g_threa
 
 int rt_set_option(rt_ctx* ctx, const char* key, int64_t value) {
     if (!ctx || !key) return set_err(ctx, RT_ERR_ARG, "null argument");
-    if (!std::strcmp(key, "traversal")) {
-        if (value != RT_TRAVERSAL_FAST && value != RT_TRAVERSAL_REF)
-            return set_err(ctx, RT_ERR_ARG, "traversal must be 0 (fast) or 1 (ref)");
-        ctx->traversal = (int)value;
-        invalidate_accum(ctx);
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "brute_near")) {
-        // no repack and no upload: the packer decides where the floor is safe whatever the option, and the floor
-        // reaches the kernels in DevScene, made for every launch (dev_scene); the frame is the same either way
-        if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "brute_near must be -1 (auto), 0 (off) or 1 (auto)");
-        ctx->brute_near = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "bvh") || !std::strcmp(key, "brute_max") || !std::strcmp(key, "brute_cluster") ||
-        !std::strcmp(key, "brute_shell")) {
-        if (!std::strcmp(key, "bvh")) {
-            if (value != RT_BVH_REFERENCE && value != RT_BVH_SAH)
-                return set_err(ctx, RT_ERR_ARG, "bvh must be 0 (reference tree) or 1 (sah)");
-            ctx->bvh_layout = (int)value;
-        } else if (!std::strcmp(key, "brute_cluster")) {
-            if (value < -1 || value > 1)
-                return set_err(ctx, RT_ERR_ARG, "brute_cluster must be -1 (auto), 0 (off) or 1 (force)");
-            ctx->brute_cluster = (int)value;
-        } else if (!std::strcmp(key, "brute_shell")) {
-            if (value < -1 || value > 1)
-                return set_err(ctx, RT_ERR_ARG, "brute_shell must be -1 (auto), 0 (off) or 1 (force)");
-            ctx->brute_shell = (int)value;
-        } else {
-            if (value < 0 || value > 4096) return set_err(ctx, RT_ERR_ARG, "brute_max must be in 0..4096");
-            ctx->brute_max = (int)value;
-        }
-        if (!ctx->have_scene) return RT_OK;
-        HostScene& hs = ctx->hs;   // repack the FAST nodes of the current scene
-        std::string why;
-        rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster,
-                         ctx->brute_shell, why);
-        for (auto& d : ctx->devs) {
-            HIP_OR_RET(ctx, hipSetDevice(d.id));
-            HIP_OR_RET(ctx, order_after_last(d, d.stream));
-            // a launch in flight on another stream may still read the buffers upload() can free
-            HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-            HIP_OR_RET(ctx, upload(d.nodes, hs.nodes, d.stream));
-            HIP_OR_RET(ctx, upload(d.wnodes, hs.wnodes, d.stream));
-            HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
-            HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
-            HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
-            HIP_OR_RET(ctx, upload_cbox(d, hs));
-            HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
-            HIP_OR_RET(ctx, upload(d.tri_geo, hs.tri_geo, d.stream));
-            HIP_OR_RET(ctx, upload(d.tri_fast, hs.tri_fast, d.stream));
-            HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
-            HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-        }
-        if (!hs.fast_ok) ctx->err = "FAST traversal unavailable (" + why + "); REF traversal will be used";
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "resume_min")) {
-        if (value < -1 || value > 64) return set_err(ctx, RT_ERR_ARG, "resume_min must be -1 (auto) or 0..64");
-        ctx->resume_min = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "team")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-            return set_err(ctx, RT_ERR_ARG, "team must be 0 (auto), 1, 2, 4 or 8");
-        ctx->team = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "walk_team")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-            return set_err(ctx, RT_ERR_ARG, "walk_team must be 0 (auto), 1, 2, 4 or 8");
-        ctx->walk_team = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "sun_any")) {
-        if (value != 0 && value != 1) return set_err(ctx, RT_ERR_ARG, "sun_any must be 0 or 1");
-        ctx->sun_any = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "sun_skip")) {
-        if (value != 0 && value != 1) return set_err(ctx, RT_ERR_ARG, "sun_skip must be 0 or 1");
-        ctx->sun_skip = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "step")) {
-        if (value < 0 || value > 2) return set_err(ctx, RT_ERR_ARG, "step must be 0 (auto), 1 (item) or 2 (round)");
-        ctx->step = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "waves")) {
-        if (value < 0 || value > 8) return set_err(ctx, RT_ERR_ARG, "waves must be in 0..8");
-        ctx->max_waves = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "pilot")) {
-        if (value < -1 || value > (1 << 20)) return set_err(ctx, RT_ERR_ARG, "pilot must be -1 (auto), 0 (off) or a sample count");
-        ctx->pilot = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "pilot_chunk")) {
-        if (value < 0 || value > 4096) return set_err(ctx, RT_ERR_ARG, "pilot_chunk must be in 0..4096 (0 = auto)");
-        ctx->pilot_chunk = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "pilot_levels")) {
-        if (value != 0 && (value < 2 || value > 256)) return set_err(ctx, RT_ERR_ARG, "pilot_levels must be 0 (auto) or 2..256");
-        ctx->pilot_levels = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "stack_lds")) {
-        if (value != 0 && (value < kStackLdsMin || value > rt::kStackLds))
-            return set_err(ctx, RT_ERR_ARG, "stack_lds must be 0 (auto) or %d..%d", kStackLdsMin, rt::kStackLds);
-        ctx->stack_lds = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "sun_cache")) {
-        if (value != 0 && value != 1) return set_err(ctx, RT_ERR_ARG, "sun_cache must be 0 or 1");
-        ctx->sun_cache = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "fixed_point")) {
-        if (value != 0 && value != 1) return set_err(ctx, RT_ERR_ARG, "fixed_point must be 0 or 1");
-        ctx->fixed_point = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "bvh_width")) {
-        if (value != 0 && value != 2 && value != 4) return set_err(ctx, RT_ERR_ARG, "bvh_width must be 0 (auto), 2 or 4");
-        ctx->bvh_width = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "ref_stack")) {
-        if (value < 20 || value > 64) return set_err(ctx, RT_ERR_ARG, "ref_stack must be in 20..64 (20 = the reference's)");
-        ctx->ref_stack = (int)value;
-        invalidate_accum(ctx);
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "slices")) {
-        if (value < -1 || value > 16) return set_err(ctx, RT_ERR_ARG, "slices must be -1 (auto), 0 (off) or 1..16");
-        ctx->slices = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "brute_refill")) {
-        if (value < -1 || value > rt::kRefillMax)
-            return set_err(ctx, RT_ERR_ARG, "brute_refill must be -1 (auto), 0 or 1 (off) or 2..%d", rt::kRefillMax);
-        ctx->brute_refill = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "denoise_lds")) {
-        if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "denoise_lds must be -1 (auto), 0 or 1");
-        ctx->denoise_lds = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "query_engine")) {
-        if (value < 0 || value > 2) return set_err(ctx, RT_ERR_ARG, "query_engine must be 0 (auto), 1 (plain) or 2 (persistent)");
-        ctx->query_engine = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "query_grid")) {
-        if (value < 0 || value > (1 << 20)) return set_err(ctx, RT_ERR_ARG, "query_grid must be 0 (auto) or a block count");
-        ctx->query_grid = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "wdq")) {
-        if (value != 0 && value != 1) return set_err(ctx, RT_ERR_ARG, "wdq must be 0 or 1");
-        ctx->wdq = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "handout")) {
-        if (value < -1 || value > 1) return set_err(ctx, RT_ERR_ARG, "handout must be -1 (auto), 0 or 1");
-        ctx->handout = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "spec")) {
-        if (value != -1 && value != 0 && value != 2 && value != 4 && value != 8)
-            return set_err(ctx, RT_ERR_ARG, "spec must be -1 (auto), 0 (off), 2, 4 or 8");
-        ctx->spec = (int)value;
-        return RT_OK;
-    }
-    if (!std::strcmp(key, "block")) {
-        if (value != 64 && value != 128 && value != 256) return set_err(ctx, RT_ERR_ARG, "block must be 64/128/256");
-        ctx->block = (int)value;
-        return RT_OK;
+    for (const Option& o : options()) {
+        if (std::strcmp(key, o.key)) continue;
+        if (!o.accepts(value)) return set_err(ctx, RT_ERR_ARG, "%s", o.message.c_str());
+        ctx->*o.field = (int)value;
+        if (o.effect == Effect::kInvalidate) invalidate_accum(ctx);
+        return o.effect == Effect::kRepack ? repack_scene(ctx) : RT_OK;
     }
     return set_err(ctx, RT_ERR_ARG, "unknown option '%s'", key);
 }
@@ -612,25 +591,13 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
     for (auto& d : ctx->devs) {
-        HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, order_after_last(d, d.stream));
-        // a launch in flight on another stream may still read the buffers upload() / ensure() free
-        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-        HIP_OR_RET(ctx, upload(d.nodes, hs.nodes, d.stream));
-        HIP_OR_RET(ctx, upload(d.wnodes, hs.wnodes, d.stream));
-        HIP_OR_RET(ctx, upload(d.wleaves, hs.wleaves, d.stream));
-        HIP_OR_RET(ctx, upload(d.brute, hs.brute, d.stream));
-        HIP_OR_RET(ctx, upload(d.brute_box, hs.brute_box, d.stream));
-        HIP_OR_RET(ctx, upload_cbox(d, hs));
-        HIP_OR_RET(ctx, upload(d.brute_crow, hs.brute_crow, d.stream));
-        HIP_OR_RET(ctx, ensure_stack_ovf(d, hs));
-        HIP_OR_RET(ctx, upload(d.bvh9, hs.bvh9, d.stream));
-        HIP_OR_RET(ctx, upload(d.tri_geo, hs.tri_geo, d.stream));
-        HIP_OR_RET(ctx, upload(d.tri_fast, hs.tri_fast, d.stream));
-        HIP_OR_RET(ctx, upload(d.tri_shade, hs.tri_shade, d.stream));
-        HIP_OR_RET(ctx, upload(d.mat, hs.mat, d.stream));
-        HIP_OR_RET(ctx, ensure(d.tri_frame, (size_t)std::max<int64_t>(hs.ntri, 1) * 3 * sizeof(float4)));
-        HIP_OR_RET(ctx, ensure(d.work, rt::kWorkBytes));
+        const int st = upload_fast(ctx, d, hs);
+        if (st) return st;
+        HIP_OR_RET(ctx, upload(d, d.bvh9, hs.bvh9));
+        HIP_OR_RET(ctx, upload(d, d.tri_shade, hs.tri_shade));
+        HIP_OR_RET(ctx, upload(d, d.mat, hs.mat));
+        HIP_OR_RET(ctx, grow(d, d.tri_frame, (size_t)std::max<int64_t>(hs.ntri, 1) * 3 * sizeof(float4)));
+        HIP_OR_RET(ctx, grow(d, d.work, rt::kWorkBytes));
         HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
     }
     ctx->hs = std::move(hs);
@@ -655,9 +622,8 @@ int rt_set_env(rt_ctx* ctx, const uint8_t* rgba, int w, int h) {
     for (auto& d : ctx->devs) {
         HIP_OR_RET(ctx, hipSetDevice(d.id));
         HIP_OR_RET(ctx, order_after_last(d, d.stream));
-        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));   // the old IBL buffer may be freed by ensure
-        HIP_OR_RET(ctx, ensure(d.ibl, bytes));
-        HIP_OR_RET(ctx, ensure(d.ibl_sum, (size_t)(w + 1) * (size_t)(h + 1) * sizeof(uint32_t)));
+        HIP_OR_RET(ctx, grow(d, d.ibl, bytes));
+        HIP_OR_RET(ctx, grow(d, d.ibl_sum, (size_t)(w + 1) * (size_t)(h + 1) * sizeof(uint32_t)));
         HIP_OR_RET(ctx, hipMemcpyAsync(d.ibl.p, rgba, bytes, hipMemcpyHostToDevice, d.stream));
         HIP_OR_RET(ctx, rt::launch_ibl_sum((const uchar4*)d.ibl.p, w, h, (uint32_t*)d.ibl_sum.p, d.stream));
         HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
@@ -716,10 +682,7 @@ hipError_t setup_pilot(rt_ctx* ctx, Device& d, rt::FrameParams& fp) {
     // each pixel's pass-1 RNG offset (4 B, pilot_draws)
     const size_t need = n * 40 + 2 * 256 * sizeof(uint32_t) + 2 * (n + 1) * sizeof(uint32_t) +
                         (n + 256) * sizeof(uint32_t) + n * sizeof(uint32_t);
-    hipError_t e = hipSuccess;
-    // growing frees the old buffer from the host: the last launch (any stream) may still use it
-    if (d.pilot.bytes < need && d.pending) e = hipEventSynchronize(d.done);
-    if (e == hipSuccess) e = ensure(d.pilot, need);
+    hipError_t e = grow(d, d.pilot, need);
     if (e != hipSuccess) return e;
     char* base = (char*)d.pilot.p;
     fp.pilot = k;
@@ -733,7 +696,6 @@ hipError_t setup_pilot(rt_ctx* ctx, Device& d, rt::FrameParams& fp) {
     const int64_t lanes = (int64_t)std::max(d.cus, 1) * rt::kWalkLanesPerCu;
     // up to 4 pixels per resident lane: pass 1 finishes the pixels that draw nothing (sky), and the device
     // picks trails only when the rest is at most one pixel per lane (pilot_team_pick_kernel)
-    // (auto); a set trail count applies to any tile
     // (auto); a set trail count applies to any tile.  A trail's record count shares a word with its mode
     // (rt_spec.hip): spp < 2^16
     if (ctx->spec != 0 && (ctx->spec > 0 || fp.nloc <= 4 * lanes) && fp.spp < 65536 && !use_wide(ctx) &&
@@ -745,8 +707,7 @@ hipError_t setup_pilot(rt_ctx* ctx, Device& d, rt::FrameParams& fp) {
         // 16 B, at most 1 GB on 256 CUs) no longer grows with spp
         fp.spec_cap = std::min(fp.spp - k, rt::kSpecCapMax);
         const size_t lbytes = rt::spec_log_bytes(fp, d.cus);
-        if (d.spec.bytes < lbytes && d.pending) e = hipEventSynchronize(d.done);
-        if (e == hipSuccess) e = ensure(d.spec, lbytes);
+        e = grow(d, d.spec, lbytes);
         if (e != hipSuccess) {
             if (ctx->spec > 0) return e;
             // auto: a device short of memory renders pass 2 without trails (same frame) instead of failing
@@ -805,10 +766,7 @@ hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t
     const size_t n = (size_t)fp.nloc;
     const size_t sbytes = brute ? 48 : 32;   // (the brute-force kernels' state carries the camera ray, slice_publish)
     const size_t need = n * sbytes + n * sizeof(uint32_t);
-    hipError_t e = hipSuccess;
-    // growing frees the old buffer from the host: the last launch (any stream) may still use it
-    if (d.slice.bytes < need && d.pending) e = hipEventSynchronize(d.done);
-    if (e == hipSuccess) e = ensure(d.slice, need);
+    hipError_t e = grow(d, d.slice, need);
     if (e == hipSuccess && !brute) e = hipMemsetAsync((char*)d.slice.p + n * sbytes, 0, n * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     fp.slices = brute ? offer : k;
@@ -822,14 +780,12 @@ hipError_t setup_slices(rt_ctx* ctx, Device& d, rt::FrameParams& fp, hipStream_t
 int rt_render_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5], int64_t npix, int spp,
                      int max_bounce, int row0, int row_step, float* d_out, void* stream) {
     rt::FrameParams fp;
-    int st = check_frame(ctx, cam, env, npix, spp, row0, row_step, &fp);
+    Device* dp = nullptr;
+    int st = check_frame(ctx, cam, env, npix, spp, max_bounce, row0, row_step, &fp);
+    if (!st) st = slot_of(ctx, device_index, &dp);
     if (st) return st;
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
     if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
-    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
-    fp.max_bounce = max_bounce;
-    Device& d = ctx->devs[device_index];
+    Device& d = *dp;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;  // NULL = the device's default (null) stream, HIP convention
     HIP_OR_RET(ctx, order_after_last(d, s));
@@ -868,27 +824,62 @@ void par_copy(char* dst, const char* src, size_t n) {
     for (auto& t : ts) t.join();
 }
 
-// rt_render / rt_render_rgb8: every device renders its rows (row r on device r mod n), then, for
-// rgb8 >= 0, quantizes them on the device (rgb8 = 1: gamma first) so 1 byte per channel crosses
-// PCIe; the host de-interleaves the rows into out (elem = 4 or 1 bytes per channel).
-int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,
-                 void* out, int rgb8);
-
-int render_host(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,
-                void* out, int rgb8) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int st = render_host_(ctx, cam, env, npix, spp, max_bounce, out, rgb8);
-    if (ctx) ctx->t_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
+// Rows of a frame over the slots: frame row r is row r / nd of slot r % nd's tile, and the frame's last row may be
+// partial.  gather_rows: slot k's tile-packed array (elem bytes per pixel) into the frame's order.  (static: these
+// unnamed namespaces open inside extern "C", where a function's C name stays a dynamic symbol without it)
+static void gather_rows(char* frame, const char* tile, size_t elem, int k, int nd, int W, int64_t npix) {
+    const int64_t rows = rt_tile_rows(npix, W, k, nd);
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t first = ((int64_t)k + r * nd) * W;
+        std::memcpy(frame + first * elem, tile + r * W * elem, (size_t)std::min<int64_t>(W, npix - first) * elem);
+    }
+}
+// ... and scatter_rows, its inverse: slot k's rows out of a frame-ordered array, tile-packed
+static void scatter_rows(char* tile, const char* frame, size_t elem, int k, int nd, int W, int64_t npix) {
+    const int64_t rows = rt_tile_rows(npix, W, k, nd);
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t first = ((int64_t)k + r * nd) * W;
+        std::memcpy(tile + r * W * elem, frame + first * elem, (size_t)std::min<int64_t>(W, npix - first) * elem);
+    }
 }
 
+// The read-back of the host forms, after every slot's frame is enqueued into its d.out.  Enqueue: the slot's nloc
+// pixels into its pinned stage (grow_stage came first), for rgb8 >= 0 quantised on the device (rgb8 = 1: gamma
+// first), so that 1 byte per channel crosses PCIe
+static int readback_enqueue(rt_ctx* ctx, Device& d, int64_t nloc, int rgb8) {
+    const size_t bytes = (size_t)nloc * 3 * (rgb8 >= 0 ? 1 : sizeof(float));
+    const void* src = d.out.p;
+    if (rgb8 >= 0) {
+        HIP_OR_RET(ctx, grow(d, d.out8, bytes));
+        HIP_OR_RET(ctx, rt::launch_rgb8((const float*)d.out.p, (uint8_t*)d.out8.p, nloc * 3, rgb8 == 1, d.stream));
+        src = d.out8.p;
+    }
+    HIP_OR_RET(ctx, hipMemcpyAsync(d.host_stage, src, bytes, hipMemcpyDeviceToHost, d.stream));
+    return RT_OK;
+}
+// Finish: wait for every slot; then (out != NULL) the stages into out, elem bytes per channel: one slot's stage is
+// the frame, several slots' are gathered row by row
+static int readback_finish(rt_ctx* ctx, void* out, size_t elem, int64_t npix, int W) {
+    const int nd = (int)ctx->devs.size();
+    for (int k = 0; k < nd; ++k) {
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+        if (!out) continue;
+        if (nd == 1) par_copy((char*)out, d.host_stage, (size_t)npix * 3 * elem);
+        else gather_rows((char*)out, d.host_stage, 3 * elem, k, nd, W, npix);
+    }
+    return RT_OK;
+}
+
+// rt_render / rt_render_rgb8: every device renders its rows (row r on device r mod n), then the read-back above
+// (rgb8 as there; < 0: the float frame)
 int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,
                  void* out, int rgb8) {
     rt::FrameParams fp0;
-    int st = check_frame(ctx, cam, env, npix, spp, 0, 1, &fp0);
+    int st = check_frame(ctx, cam, env, npix, spp, max_bounce, 0, 1, &fp0);
     if (st) return st;
     if (!out) return set_err(ctx, RT_ERR_ARG, "output must not be NULL");
-    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
     const int nd = (int)ctx->devs.size();
     const int W = fp0.width;
     const size_t elem = rgb8 >= 0 ? 1 : sizeof(float);
@@ -901,19 +892,11 @@ int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t n
         rt::FrameParams fp = fp0;
         fp.row0 = k;
         fp.row_step = nd;
-        fp.max_bounce = max_bounce;
         fp.nloc = rt_tile_rows(npix, W, k, nd) * W;
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        const size_t bytes = (size_t)fp.nloc * 3 * elem;
-        if (bytes == 0) continue;
-        HIP_OR_RET(ctx, ensure(d.out, (size_t)fp.nloc * 3 * sizeof(float)));
-        if (d.host_stage_bytes < bytes) {
-            if (d.host_stage) HIP_OR_RET(ctx, hipHostFree(d.host_stage));
-            d.host_stage = nullptr;
-            d.host_stage_bytes = 0;
-            HIP_OR_RET(ctx, hipHostMalloc((void**)&d.host_stage, bytes, hipHostMallocDefault));
-            d.host_stage_bytes = bytes;
-        }
+        if (fp.nloc == 0) continue;
+        HIP_OR_RET(ctx, grow(d, d.out, (size_t)fp.nloc * 3 * sizeof(float)));
+        HIP_OR_RET(ctx, grow_stage(d, (size_t)fp.nloc * 3 * elem));
         HIP_OR_RET(ctx, order_after_last(d, d.stream));
         HIP_OR_RET(ctx, setup_pilot(ctx, d, fp));
         HIP_OR_RET(ctx, setup_slices(ctx, d, fp, d.stream));
@@ -926,39 +909,23 @@ int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t n
     for (int k = 0; k < nd; ++k) {
         Device& d = ctx->devs[k];
         const int64_t nloc = rt_tile_rows(npix, W, k, nd) * W;
-        const size_t bytes = (size_t)nloc * 3 * elem;
-        if (bytes == 0) continue;
+        if (nloc == 0) continue;
         HIP_OR_RET(ctx, hipSetDevice(d.id));
         HIP_OR_RET(ctx, rt::launch_render_finish(dev_scene(ctx, d), effective_traversal(ctx), ctx->block,
                                                  (float*)d.out.p, (unsigned int*)d.work.p, d.stream, pend[k]));
         HIP_OR_RET(ctx, mark_launch(d, d.stream));
-        const void* src = d.out.p;
-        if (rgb8 >= 0) {
-            HIP_OR_RET(ctx, ensure(d.out8, bytes));
-            HIP_OR_RET(ctx, rt::launch_rgb8((const float*)d.out.p, (uint8_t*)d.out8.p, nloc * 3, rgb8 == 1,
-                                            d.stream));
-            src = d.out8.p;
-        }
-        HIP_OR_RET(ctx, hipMemcpyAsync(d.host_stage, src, bytes, hipMemcpyDeviceToHost, d.stream));
+        st = readback_enqueue(ctx, d, nloc, rgb8);
+        if (st) return st;
     }
-    char* dst = static_cast<char*>(out);
-    for (int k = 0; k < nd; ++k) {
-        Device& d = ctx->devs[k];
-        HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-        const int64_t rows = rt_tile_rows(npix, W, k, nd);
-        if (nd == 1) {
-            par_copy(dst, d.host_stage, (size_t)npix * 3 * elem);
-            continue;
-        }
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t gr = (int64_t)k + r * nd;
-            const int64_t first = gr * W;
-            const int64_t count = std::min<int64_t>(W, npix - first);
-            std::memcpy(dst + 3 * first * elem, d.host_stage + 3 * r * W * elem, (size_t)count * 3 * elem);
-        }
-    }
-    return RT_OK;
+    return readback_finish(ctx, out, elem, npix, W);
+}
+
+int render_host(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce,
+                void* out, int rgb8) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int st = render_host_(ctx, cam, env, npix, spp, max_bounce, out, rgb8);
+    if (ctx) ctx->t_render_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return st;
 }
 
 // ---- progressive accumulation (rt_accum_*) ----
@@ -981,10 +948,15 @@ int accum_close_slot(rt_ctx* ctx, Device& d) {
     if (!d.accum.p && !d.mark.p && !d.sel.p && !d.all.p) return RT_OK;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     if (d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));   // an add in flight still uses the state
-    release(d.accum);
-    release(d.mark);
-    release(d.sel);
-    release(d.all);
+    for (DevBuf* b : {&d.accum, &d.mark, &d.sel, &d.all}) b->release();
+    return RT_OK;
+}
+
+// the host forms: the open accumulation is rt_accum_begin's (every slot holds its rows of one frame)
+static int accum_host_open(rt_ctx* ctx, const char* what) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
+        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
     return RT_OK;
 }
 
@@ -1038,17 +1010,6 @@ SelView sel_view(const Device& d) {
             (uint8_t*)(b + n * 4 + 4 + rt::select_scratch_words(d.acc_nloc) * 4)};
 }
 
-// grow a per-slot buffer of the accumulation (growing frees the old one from the host: the last launch, on
-// any stream, may still use it)
-hipError_t accum_ensure(Device& d, DevBuf& b, size_t need) {
-    need = std::max<size_t>(need, 16);
-    if (b.bytes < need && d.pending) {
-        hipError_t e = hipEventSynchronize(d.done);
-        if (e != hipSuccess) return e;
-    }
-    return ensure(b, need);
-}
-
 // the slot's tile as check_frame describes it (row tiling, width, npix), for the select kernels
 void accum_tile(const Device& d, rt::FrameParams& fp) {
     fp = rt::FrameParams{};
@@ -1059,22 +1020,19 @@ void accum_tile(const Device& d, rt::FrameParams& fp) {
     fp.nloc = d.acc_nloc;
 }
 
+// the slot, its accumulation usable and holding samples
 int accum_slot_of(rt_ctx* ctx, int device_index, const char* what, Device** out) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
-    Device& d = ctx->devs[device_index];
-    const int st = accum_slot_usable(ctx, d, what);
+    int st = slot_of(ctx, device_index, out);
+    if (!st) st = accum_slot_usable(ctx, **out, what);
     if (st) return st;
-    if (d.acc_samples == 0) return set_err(ctx, RT_ERR_STATE, "%s: the accumulation has no samples yet", what);
-    *out = &d;
+    if ((*out)->acc_samples == 0) return set_err(ctx, RT_ERR_STATE, "%s: the accumulation has no samples yet", what);
     return RT_OK;
 }
 
 // flags -> the ordered list (what: 0 the error measure against the mark, 1 a tile-packed device mask, 2 all)
 int accum_select_slot(rt_ctx* ctx, Device& d, int what, float threshold, const uint8_t* d_mask, hipStream_t s) {
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, accum_ensure(d, d.sel, sel_bytes(d.acc_nloc)));
+    HIP_OR_RET(ctx, grow(d, d.sel, sel_bytes(d.acc_nloc)));
     const SelView v = sel_view(d);
     rt::FrameParams fp;
     accum_tile(d, fp);
@@ -1095,9 +1053,8 @@ int accum_select_slot(rt_ctx* ctx, Device& d, int what, float threshold, const u
 // the host forms of the selects: every slot's select on its own stream, then the lengths read back
 int accum_select_host(rt_ctx* ctx, int what, float threshold, const uint8_t* mask, int64_t* n_selected,
                       const char* name) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", name);
+    const int open = accum_host_open(ctx, name);
+    if (open) return open;
     if (what == 1 && !mask) return set_err(ctx, RT_ERR_ARG, "%s: mask must not be NULL", name);
     const int nd = (int)ctx->devs.size();
     for (int k = 0; k < nd; ++k) {
@@ -1115,12 +1072,8 @@ int accum_select_host(rt_ctx* ctx, int what, float threshold, const uint8_t* mas
         const uint8_t* d_mask = nullptr;
         if (what == 1 && d.acc_nloc > 0) {   // the slot's rows of the mask, tile-packed, staged in d.out8
             tiles[k].assign((size_t)d.acc_nloc, 0);
-            const int64_t rows = rt_tile_rows(npix, W, k, nd);
-            for (int64_t r = 0; r < rows; ++r) {
-                const int64_t first = ((int64_t)k + r * nd) * W;
-                std::memcpy(tiles[k].data() + r * W, mask + first, (size_t)std::min<int64_t>(W, npix - first));
-            }
-            HIP_OR_RET(ctx, accum_ensure(d, d.out8, (size_t)d.acc_nloc));
+            scatter_rows((char*)tiles[k].data(), (const char*)mask, 1, k, nd, W, npix);
+            HIP_OR_RET(ctx, grow(d, d.out8, (size_t)d.acc_nloc));
             HIP_OR_RET(ctx, order_after_last(d, d.stream));
             HIP_OR_RET(ctx, hipMemcpyAsync(d.out8.p, tiles[k].data(), (size_t)d.acc_nloc, hipMemcpyHostToDevice, d.stream));
             d_mask = (const uint8_t*)d.out8.p;
@@ -1156,12 +1109,7 @@ int accum_gather_host(rt_ctx* ctx, void* out, size_t elem, const void* (*src)(De
         HIP_OR_RET(ctx, order_after_last(d, d.stream));
         HIP_OR_RET(ctx, hipMemcpyAsync(tile.data(), src(d), tile.size(), hipMemcpyDeviceToHost, d.stream));
         HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-        const int64_t rows = rt_tile_rows(npix, W, k, nd);
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t first = ((int64_t)k + r * nd) * W;
-            std::memcpy((char*)out + first * elem, tile.data() + r * W * elem,
-                        (size_t)std::min<int64_t>(W, npix - first) * elem);
-        }
+        gather_rows((char*)out, tile.data(), elem, k, nd, W, npix);
     }
     return RT_OK;
 }
@@ -1170,9 +1118,8 @@ int accum_gather_host(rt_ctx* ctx, void* out, size_t elem, const void* (*src)(De
 // the frame back as render_host_ does (rgb8 >= 0: quantised on the devices first); out may be NULL for an add
 // (selected: rt_accum_add_selected -- the add runs on each slot's selection)
 int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char* what, bool selected = false) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
+    const int open = accum_host_open(ctx, what);
+    if (open) return open;
     const int nd = (int)ctx->devs.size();
     for (int k = 0; k < nd; ++k) {
         const int st = read       ? accum_slot_usable(ctx, ctx->devs[k], what)
@@ -1189,16 +1136,9 @@ int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char*
     // every slot's launch is enqueued before the host waits for any
     for (int k = 0; k < nd; ++k) {
         Device& d = ctx->devs[k];
-        const size_t bytes = (size_t)d.acc_nloc * 3 * elem;
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, ensure(d.out, std::max<size_t>((size_t)d.acc_nloc * 3 * sizeof(float), 16)));
-        if (out && d.host_stage_bytes < bytes) {
-            if (d.host_stage) HIP_OR_RET(ctx, hipHostFree(d.host_stage));
-            d.host_stage = nullptr;
-            d.host_stage_bytes = 0;
-            HIP_OR_RET(ctx, hipHostMalloc((void**)&d.host_stage, bytes, hipHostMallocDefault));
-            d.host_stage_bytes = bytes;
-        }
+        HIP_OR_RET(ctx, grow(d, d.out, (size_t)d.acc_nloc * 3 * sizeof(float)));
+        if (out) HIP_OR_RET(ctx, grow_stage(d, (size_t)d.acc_nloc * 3 * elem));
         if (!read) {
             const int st = selected ? rt_accum_add_selected_device(ctx, k, spp, (float*)d.out.p, d.stream)
                                     : rt_accum_add_device(ctx, k, spp, (float*)d.out.p, d.stream);
@@ -1208,53 +1148,26 @@ int accum_host(rt_ctx* ctx, int spp, bool read, void* out, int rgb8, const char*
             HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, (float*)d.out.p, d.acc_nloc, d.stream));
             HIP_OR_RET(ctx, mark_launch(d, d.stream));
         }
-        if (!out || bytes == 0) continue;
-        const void* src = d.out.p;
-        if (rgb8 >= 0) {
-            HIP_OR_RET(ctx, ensure(d.out8, bytes));
-            HIP_OR_RET(ctx, rt::launch_rgb8((const float*)d.out.p, (uint8_t*)d.out8.p, d.acc_nloc * 3, rgb8 == 1,
-                                            d.stream));
-            src = d.out8.p;
-        }
-        HIP_OR_RET(ctx, hipMemcpyAsync(d.host_stage, src, bytes, hipMemcpyDeviceToHost, d.stream));
+        if (!out || d.acc_nloc == 0) continue;
+        const int st = readback_enqueue(ctx, d, d.acc_nloc, rgb8);
+        if (st) return st;
     }
-    char* dst = static_cast<char*>(out);
-    for (int k = 0; k < nd; ++k) {
-        Device& d = ctx->devs[k];
-        HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
-        if (!out) continue;
-        const int64_t rows = rt_tile_rows(npix, W, k, nd);
-        if (nd == 1) {
-            par_copy(dst, d.host_stage, (size_t)npix * 3 * elem);
-            continue;
-        }
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t first = ((int64_t)k + r * nd) * W;
-            const int64_t count = std::min<int64_t>(W, npix - first);
-            std::memcpy(dst + 3 * first * elem, d.host_stage + 3 * r * W * elem, (size_t)count * 3 * elem);
-        }
-    }
-    return RT_OK;
+    return readback_finish(ctx, out, elem, npix, W);
 }
 }  // namespace
 
 int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5], int64_t npix,
                           int max_bounce, int row0, int row_step) {
     rt::FrameParams fp;
-    int st = check_frame(ctx, cam, env, npix, 0, row0, row_step, &fp);
+    Device* dp = nullptr;
+    int st = check_frame(ctx, cam, env, npix, 0, max_bounce, row0, row_step, &fp);
+    if (!st) st = slot_of(ctx, device_index, &dp);
     if (st) return st;
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
-    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
-    Device& d = ctx->devs[device_index];
+    Device& d = *dp;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     d.acc_open = false;   // replaces the slot's accumulation
     d.acc_valid = false;
-    const size_t need = std::max<size_t>((size_t)fp.nloc * 2 * sizeof(float4), 16);
-    // growing frees the old buffer from the host: the last launch (any stream) may still use it
-    if (d.accum.bytes < need && d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));
-    HIP_OR_RET(ctx, ensure(d.accum, need));
+    HIP_OR_RET(ctx, grow(d, d.accum, (size_t)fp.nloc * 2 * sizeof(float4)));
     std::memcpy(d.acc_cam, cam, sizeof d.acc_cam);
     std::memcpy(d.acc_env, env, sizeof d.acc_env);
     d.acc_npix = npix;
@@ -1271,25 +1184,24 @@ int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], co
 }
 
 int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
-    Device& d = ctx->devs[device_index];
-    int st = accum_check_add(ctx, d, spp);
+    Device* dp = nullptr;
+    int st = slot_of(ctx, device_index, &dp);
+    if (!st) st = accum_check_add(ctx, *dp, spp);
     if (st) return st;
+    Device& d = *dp;
     rt::FrameParams fp;
     // the frame as begun, at the samples done after this add, under the options as they are now
-    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, (int)(d.acc_samples + spp), d.acc_row0, d.acc_row_step, &fp);
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, (int)(d.acc_samples + spp), d.acc_max_bounce, d.acc_row0,
+                     d.acc_row_step, &fp);
     if (st) return st;
     if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
-    fp.max_bounce = d.acc_max_bounce;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, order_after_last(d, s));
     if (!d.acc_uniform && fp.nloc > 0) {
         // the pixels' counts differ (rt_accum_add_selected): the listed kernel over every pixel, each from its own
         // count, then the frame resolved from the state (pixel by pixel the divisor differs)
-        HIP_OR_RET(ctx, accum_ensure(d, d.all, (size_t)fp.nloc * 4 + 4));
+        HIP_OR_RET(ctx, grow(d, d.all, (size_t)fp.nloc * 4 + 4));
         uint32_t* all = (uint32_t*)d.all.p;
         if (!d.acc_all_ready) HIP_OR_RET(ctx, rt::launch_list_all(all, fp.nloc, all + fp.nloc, s));
         d.acc_all_ready = true;
@@ -1321,9 +1233,8 @@ int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, vo
 
 int rt_accum_begin(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int max_bounce) {
     rt::FrameParams fp;
-    int st = check_frame(ctx, cam, env, npix, 0, 0, 1, &fp);
+    int st = check_frame(ctx, cam, env, npix, 0, max_bounce, 0, 1, &fp);
     if (st) return st;
-    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
     const int nd = (int)ctx->devs.size();
     for (int k = 0; k < nd; ++k) {
         st = rt_accum_begin_device(ctx, k, cam, env, npix, max_bounce, k, nd);
@@ -1370,7 +1281,7 @@ int rt_accum_mark_device(rt_ctx* ctx, int device_index, void* stream) {
     Device& d = *dp;
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, accum_ensure(d, d.mark, (size_t)d.acc_nloc * sizeof(float4)));
+    HIP_OR_RET(ctx, grow(d, d.mark, (size_t)d.acc_nloc * sizeof(float4)));
     HIP_OR_RET(ctx, order_after_last(d, s));
     d.acc_marked = false;
     HIP_OR_RET(ctx, rt::launch_accum_mark((const float4*)d.accum.p, (float4*)d.mark.p, d.acc_nloc, s));
@@ -1403,17 +1314,15 @@ int rt_accum_select_all_device(rt_ctx* ctx, int device_index, void* stream) {
 }
 
 int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* d_out, void* stream) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
-    Device& d = ctx->devs[device_index];
-    int st = accum_check_add_selected(ctx, d, spp);
+    Device* dp = nullptr;
+    int st = slot_of(ctx, device_index, &dp);
+    if (!st) st = accum_check_add_selected(ctx, *dp, spp);
     if (st) return st;
+    Device& d = *dp;
     rt::FrameParams fp;
-    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, spp, d.acc_row0, d.acc_row_step, &fp);
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, spp, d.acc_max_bounce, d.acc_row0, d.acc_row_step, &fp);
     if (st) return st;
     if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
-    fp.max_bounce = d.acc_max_bounce;
     if (fp.nloc <= 0) return RT_OK;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;
@@ -1435,9 +1344,8 @@ int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* 
 }
 
 int rt_accum_mark(rt_ctx* ctx) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "rt_accum_mark: no accumulation is open (rt_accum_begin)");
+    const int open = accum_host_open(ctx, "rt_accum_mark");
+    if (open) return open;
     for (int k = 0; k < (int)ctx->devs.size(); ++k) {
         const int st = rt_accum_mark_device(ctx, k, ctx->devs[k].stream);
         if (st) return st;
@@ -1456,9 +1364,8 @@ int rt_accum_select_mask(rt_ctx* ctx, const uint8_t* mask) {
 int rt_accum_select_all(rt_ctx* ctx) { return accum_select_host(ctx, 2, 0.0f, nullptr, nullptr, "rt_accum_select_all"); }
 
 int rt_accum_selection(rt_ctx* ctx, uint8_t* mask_out) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "rt_accum_selection: no accumulation is open (rt_accum_begin)");
+    const int open = accum_host_open(ctx, "rt_accum_selection");
+    if (open) return open;
     if (!mask_out) return set_err(ctx, RT_ERR_ARG, "mask_out must not be NULL");
     for (const auto& d : ctx->devs) {
         const int st = accum_slot_usable(ctx, d, "rt_accum_selection");
@@ -1469,9 +1376,8 @@ int rt_accum_selection(rt_ctx* ctx, uint8_t* mask_out) {
 }
 
 int rt_accum_sample_map(rt_ctx* ctx, int32_t* out) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "rt_accum_sample_map: no accumulation is open (rt_accum_begin)");
+    const int open = accum_host_open(ctx, "rt_accum_sample_map");
+    if (open) return open;
     if (!out) return set_err(ctx, RT_ERR_ARG, "out must not be NULL");
     for (int k = 0; k < (int)ctx->devs.size(); ++k) {
         Device* dp = nullptr;
@@ -1480,7 +1386,7 @@ int rt_accum_sample_map(rt_ctx* ctx, int32_t* out) {
     }
     for (auto& d : ctx->devs) {   // the counts out of the state, staged in d.out
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, accum_ensure(d, d.out, (size_t)d.acc_nloc * sizeof(int32_t)));
+        HIP_OR_RET(ctx, grow(d, d.out, (size_t)d.acc_nloc * sizeof(int32_t)));
         HIP_OR_RET(ctx, order_after_last(d, d.stream));
         HIP_OR_RET(ctx, rt::launch_sample_map((const float4*)d.accum.p, (int32_t*)d.out.p, d.acc_nloc, d.stream));
         HIP_OR_RET(ctx, mark_launch(d, d.stream));
@@ -1509,15 +1415,12 @@ int denoise_params(rt_ctx* ctx, const rt_denoise_params* in, rt_denoise_params* 
 
 // the open host accumulation, every slot usable and holding samples (the checks of rt_accum_read)
 int accum_host_readable(rt_ctx* ctx, const char* what) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (!ctx->accum_host || ctx->devs.empty() || !ctx->devs[0].acc_open)
-        return set_err(ctx, RT_ERR_STATE, "%s: no accumulation is open (rt_accum_begin)", what);
-    for (int k = 0; k < (int)ctx->devs.size(); ++k) {
+    int st = accum_host_open(ctx, what);
+    for (int k = 0; !st && k < (int)ctx->devs.size(); ++k) {
         Device* dp = nullptr;
-        const int st = accum_slot_of(ctx, k, what, &dp);
-        if (st) return st;
+        st = accum_slot_of(ctx, k, what, &dp);
     }
-    return RT_OK;
+    return st;
 }
 }  // namespace
 
@@ -1529,11 +1432,11 @@ int rt_accum_guides_device(rt_ctx* ctx, int device_index, float* d_guides, void*
     if (!d_guides) return set_err(ctx, RT_ERR_ARG, "rt_accum_guides: the output must not be NULL");
     if ((uintptr_t)d_guides & 15) return set_err(ctx, RT_ERR_ARG, "rt_accum_guides: d_guides must be 16-byte aligned");
     rt::FrameParams fp;
-    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, 0, d.acc_row0, d.acc_row_step, &fp);
+    st = check_frame(ctx, d.acc_cam, d.acc_env, d.acc_npix, 0, d.acc_max_bounce, d.acc_row0, d.acc_row_step, &fp);
     if (st) return st;
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, accum_ensure(d, d.dn_const, rt::launch_const_bytes()));
+    HIP_OR_RET(ctx, grow(d, d.dn_const, rt::launch_const_bytes()));
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_accum_guides(dev_scene(ctx, d), fp, (const float4*)d.accum.p, d.dn_const.p,
                                             (float4*)d_guides, s));
@@ -1548,7 +1451,7 @@ int rt_accum_guides(rt_ctx* ctx, float* out) {
     for (int k = 0; k < (int)ctx->devs.size(); ++k) {
         Device& d = ctx->devs[k];
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, accum_ensure(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
+        HIP_OR_RET(ctx, grow(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
         st = rt_accum_guides_device(ctx, k, (float*)d.guides.p, d.stream);
         if (st) return st;
     }
@@ -1557,20 +1460,19 @@ int rt_accum_guides(rt_ctx* ctx, float* out) {
 
 int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const float* d_guides, int64_t npix, int width,
                       const rt_denoise_params* params, float* d_out, void* stream) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
+    Device* dp = nullptr;
     rt_denoise_params P;
-    const int st = denoise_params(ctx, params, &P);
+    int st = slot_of(ctx, device_index, &dp);
+    if (!st) st = denoise_params(ctx, params, &P);
     if (st) return st;
     if (!d_rgb || !d_guides || !d_out) return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: NULL buffer");
     if ((uintptr_t)d_guides & 15) return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: d_guides must be 16-byte aligned");
     if (npix < 1 || npix > 0x7fffffff || width < 1)
         return set_err(ctx, RT_ERR_ARG, "rt_denoise_device: bad frame (%lld pixels, rows of %d)", (long long)npix, width);
-    Device& d = ctx->devs[device_index];
+    Device& d = *dp;
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, accum_ensure(d, d.dn, rt::denoise_scratch_bytes(npix)));
+    HIP_OR_RET(ctx, grow(d, d.dn, rt::denoise_scratch_bytes(npix)));
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_denoise(d_rgb, (const float4*)d_guides, npix, width, P.passes, P.normal_squarings,
                                        P.sigma_c, P.sigma_p, (ctx->denoise_lds >= 0 ? ctx->denoise_lds : kDenoiseLds) != 0,
@@ -1593,8 +1495,8 @@ int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rg
     for (int k = 0; k < nd; ++k) {
         Device& d = ctx->devs[k];
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, accum_ensure(d, d.out, (size_t)d.acc_nloc * 3 * sizeof(float)));
-        HIP_OR_RET(ctx, accum_ensure(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
+        HIP_OR_RET(ctx, grow(d, d.out, (size_t)d.acc_nloc * 3 * sizeof(float)));
+        HIP_OR_RET(ctx, grow(d, d.guides, (size_t)d.acc_nloc * 12 * sizeof(float)));
         if (d.acc_nloc > 0) {
             HIP_OR_RET(ctx, order_after_last(d, d.stream));
             HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, (float*)d.out.p, d.acc_nloc, d.stream));
@@ -1615,8 +1517,8 @@ int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rg
         st = accum_gather_host(ctx, h_guides.data(), 12 * sizeof(float), [](Device& d) { return (const void*)d.guides.p; });
         if (st) return st;
         HIP_OR_RET(ctx, hipSetDevice(d0.id));
-        HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_rgb, h_rgb.size() * sizeof(float)));
-        HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_guides, h_guides.size() * sizeof(float)));
+        HIP_OR_RET(ctx, grow(d0, d0.dn_rgb, h_rgb.size() * sizeof(float)));
+        HIP_OR_RET(ctx, grow(d0, d0.dn_guides, h_guides.size() * sizeof(float)));
         HIP_OR_RET(ctx, order_after_last(d0, d0.stream));
         HIP_OR_RET(ctx, hipMemcpyAsync(d0.dn_rgb.p, h_rgb.data(), h_rgb.size() * sizeof(float), hipMemcpyHostToDevice, d0.stream));
         HIP_OR_RET(ctx, hipMemcpyAsync(d0.dn_guides.p, h_guides.data(), h_guides.size() * sizeof(float), hipMemcpyHostToDevice,
@@ -1626,7 +1528,7 @@ int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rg
         guides = (const float*)d0.dn_guides.p;
     }
     HIP_OR_RET(ctx, hipSetDevice(d0.id));
-    HIP_OR_RET(ctx, accum_ensure(d0, d0.dn_out, (size_t)npix * 3 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d0, d0.dn_out, (size_t)npix * 3 * sizeof(float)));
     st = rt_denoise_device(ctx, 0, rgb, guides, npix, W, &P, (float*)d0.dn_out.p, d0.stream);
     if (st) return st;
     HIP_OR_RET(ctx, hipMemcpyAsync(out_rgb, d0.dn_out.p, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, d0.stream));
@@ -1647,14 +1549,14 @@ int rt_render_rgb8(rt_ctx* ctx, const float cam[10], const float env[5], int64_t
 
 int rt_rgb8_device(rt_ctx* ctx, int device_index, const float* d_in, uint8_t* d_out, int64_t n, int gamma,
                    void* stream) {
-    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device_index %d out of range", device_index);
+    Device* dp = nullptr;
+    const int st = slot_of(ctx, device_index, &dp, "device_index");
+    if (st) return st;
     if (n < 0 || (n > 0 && (!d_in || !d_out)) || (gamma != 0 && gamma != 1))
         return set_err(ctx, RT_ERR_ARG, "bad arguments");
     if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 3))
         return set_err(ctx, RT_ERR_ARG, "d_in must be 16-byte and d_out 4-byte aligned");
-    HIP_OR_RET(ctx, hipSetDevice(ctx->devs[device_index].id));
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
     HIP_OR_RET(ctx, rt::launch_rgb8(d_in, d_out, n, gamma == 1, (hipStream_t)stream));
     return RT_OK;
 }
@@ -1666,8 +1568,8 @@ int rt_rgb8(rt_ctx* ctx, const float* in, uint8_t* out, int64_t n, int gamma) {
     if (n == 0) return RT_OK;
     Device& d = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, ensure(d.scratch_a, (size_t)n * sizeof(float)));
-    HIP_OR_RET(ctx, ensure(d.scratch_b, (size_t)n));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, (size_t)n * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, (size_t)n));
     HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, in, (size_t)n * sizeof(float), hipMemcpyHostToDevice, d.stream));
     HIP_OR_RET(ctx, rt::launch_rgb8((const float*)d.scratch_a.p, (uint8_t*)d.scratch_b.p, n, gamma == 1, d.stream));
     HIP_OR_RET(ctx, hipMemcpyAsync(out, d.scratch_b.p, (size_t)n, hipMemcpyDeviceToHost, d.stream));
@@ -1681,17 +1583,15 @@ std::atomic<long long> g_refill_events{0}, g_refill_lanes{0};
 int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix, int spp, int max_bounce, int row0,
               int row_step, uint64_t* counts, int n) {
     rt::FrameParams fp;
-    int st = check_frame(ctx, cam, env, npix, spp, row0, row_step, &fp);
+    int st = check_frame(ctx, cam, env, npix, spp, max_bounce, row0, row_step, &fp);
     if (st) return st;
     if (!counts) return set_err(ctx, RT_ERR_ARG, "counts must not be NULL");
-    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
-    fp.max_bounce = max_bounce;
     Device& d = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t bytes = (size_t)fp.nloc * 3 * sizeof(float);
-    HIP_OR_RET(ctx, ensure(d.out, bytes > 0 ? bytes : 16));
+    HIP_OR_RET(ctx, grow(d, d.out, bytes));
     unsigned long long h[18] = {0};   // the kernels' counters (rt_device.h NCOUNTS), then render_kernel's refill events [15] and lanes refilled [16]
-    HIP_OR_RET(ctx, ensure(d.counts, sizeof h));
+    HIP_OR_RET(ctx, grow(d, d.counts, sizeof h));
     HIP_OR_RET(ctx, hipMemsetAsync(d.counts.p, 0, sizeof h, d.stream));
     HIP_OR_RET(ctx, order_after_last(d, d.stream));
     // the instrumented brute-force launch takes sample slices as the product launch does (the tree walk's
@@ -1745,8 +1645,8 @@ int rt_gamma(rt_ctx* ctx, const float* in, float* out, int64_t n) {
     Device& d = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t bytes = (size_t)n * sizeof(float);
-    HIP_OR_RET(ctx, ensure(d.scratch_a, bytes));
-    HIP_OR_RET(ctx, ensure(d.scratch_b, bytes));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, bytes));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, bytes));
     HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, in, bytes, hipMemcpyHostToDevice, d.stream));
     HIP_OR_RET(ctx, rt::launch_gamma((const float*)d.scratch_a.p, (float*)d.scratch_b.p, n, d.stream));
     HIP_OR_RET(ctx, hipMemcpyAsync(out, d.scratch_b.p, bytes, hipMemcpyDeviceToHost, d.stream));
@@ -1769,11 +1669,8 @@ int query_check(rt_ctx* ctx, const void* rays, int64_t n, int mode, const void* 
 
 // one slot's launch: ordered with the context's other launches, never waits
 int query_enqueue(rt_ctx* ctx, Device& d, const float* d_rays, int64_t n, int mode, rt_hit* d_out, hipStream_t s) {
-    HIP_OR_RET(ctx, ensure(d.q_counter, 256));
-    const bool wide = use_wide(ctx);
-    const rt::QueryOptions q{ctx->query_engine, ctx->query_grid,
-                             ctx->resume_min >= 0 ? ctx->resume_min : wide ? kResumeMinWide : kResumeMinBvh2,
-                             ctx->max_waves, ctx->block};
+    HIP_OR_RET(ctx, grow(d, d.q_counter, 256));
+    const rt::QueryOptions q{ctx->query_engine, ctx->query_grid, resume_min_of(ctx), ctx->max_waves, ctx->block};
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_query(dev_scene(ctx, d), ctx->traversal, mode == RT_QUERY_ANY, (const float4*)d_rays,
                                      (float4*)d_out, n, q, (unsigned int*)d.q_counter.p, s));
@@ -1784,18 +1681,17 @@ int query_enqueue(rt_ctx* ctx, Device& d, const float* d_rays, int64_t n, int mo
 
 int rt_trace_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, int mode, rt_hit* d_out,
                     void* stream) {
-    const int st = query_check(ctx, d_rays, n, mode, d_out);
+    Device* dp = nullptr;
+    int st = query_check(ctx, d_rays, n, mode, d_out);
+    if (!st) st = slot_of(ctx, device_index, &dp);
     if (st) return st;
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-        return set_err(ctx, RT_ERR_ARG, "device index %d out of range", device_index);
     if (n == 0) return RT_OK;
     const uintptr_t r0 = (uintptr_t)d_rays, o0 = (uintptr_t)d_out;
     if ((r0 & 15) || (o0 & 15)) return set_err(ctx, RT_ERR_ARG, "d_rays and d_out must be 16-byte aligned");
     if (r0 < o0 + (uintptr_t)n * sizeof(rt_hit) && o0 < r0 + (uintptr_t)n * 32)
         return set_err(ctx, RT_ERR_ARG, "d_rays and d_out must not overlap");
-    Device& d = ctx->devs[device_index];
-    HIP_OR_RET(ctx, hipSetDevice(d.id));
-    return query_enqueue(ctx, d, d_rays, n, mode, d_out, (hipStream_t)stream);
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    return query_enqueue(ctx, *dp, d_rays, n, mode, d_out, (hipStream_t)stream);
 }
 
 int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out) {
@@ -1809,8 +1705,8 @@ int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out) {
         if (m <= 0) continue;
         Device& d = ctx->devs[k];
         HIP_OR_RET(ctx, hipSetDevice(d.id));
-        HIP_OR_RET(ctx, ensure(d.q_rays, (size_t)m * 32));
-        HIP_OR_RET(ctx, ensure(d.q_out, (size_t)m * sizeof(rt_hit)));
+        HIP_OR_RET(ctx, grow(d, d.q_rays, (size_t)m * 32));
+        HIP_OR_RET(ctx, grow(d, d.q_out, (size_t)m * sizeof(rt_hit)));
         HIP_OR_RET(ctx, hipMemcpyAsync(d.q_rays.p, rays + 8 * b, (size_t)m * 32, hipMemcpyHostToDevice, d.stream));
         const int qs = query_enqueue(ctx, d, (const float*)d.q_rays.p, m, mode, (rt_hit*)d.q_out.p, d.stream);
         if (qs) return qs;
@@ -1829,7 +1725,7 @@ int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* ou
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t bytes = (size_t)n * sizeof(float);
     if (!bytes) return RT_OK;
-    HIP_OR_RET(ctx, ensure(d.scratch_a, 3 * bytes));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, 3 * bytes));
     float* dx = (float*)d.scratch_a.p;
     float* dy = dx + n;
     float* dout = dy + n;
@@ -1857,8 +1753,8 @@ int rt_debug_fn(rt_ctx* ctx, int fn, const float* in, float* out, int64_t n) {
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t ibytes = (size_t)n * wi * sizeof(float);
     const size_t obytes = ((size_t)n * wo * sizeof(float) + 15) & ~(size_t)15;
-    HIP_OR_RET(ctx, ensure(d.scratch_a, ibytes));
-    HIP_OR_RET(ctx, ensure(d.scratch_b, obytes + rt::debug_fn_scratch_bytes(fn, n)));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, ibytes));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, obytes + rt::debug_fn_scratch_bytes(fn, n)));
     HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, in, ibytes, hipMemcpyHostToDevice, d.stream));
     HIP_OR_RET(ctx, order_after_last(d, d.stream));
     HIP_OR_RET(ctx, rt::launch_debug_fn(dev_scene(ctx, d), fn, (const float*)d.scratch_a.p, (float*)d.scratch_b.p, n,
@@ -1876,8 +1772,8 @@ int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, in
     if (!n) return RT_OK;
     Device& d = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d.id));
-    HIP_OR_RET(ctx, ensure(d.scratch_a, (size_t)n * 6 * sizeof(float)));
-    HIP_OR_RET(ctx, ensure(d.scratch_b, (size_t)n * 2 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, (size_t)n * 6 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, (size_t)n * 2 * sizeof(float)));
     HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, d.stream));
     HIP_OR_RET(ctx, order_after_last(d, d.stream));
     HIP_OR_RET(ctx, rt::launch_debug_trace(dev_scene(ctx, d), traversal, (const float*)d.scratch_a.p,
@@ -1893,18 +1789,18 @@ int rt_debug_pixel_log(rt_ctx* ctx, int traversal, const float cam[10], const fl
     if (!cam) return set_err(ctx, RT_ERR_ARG, "null cam");
     const int W = (int)cam[6];
     if (W <= 0 || pixel < 0 || pixel >= npix) return set_err(ctx, RT_ERR_ARG, "pixel out of range");
-    int st = check_frame(ctx, cam, env, npix, spp, (int)(pixel / W), (int)npix, &fp);
+    int st = check_frame(ctx, cam, env, npix, spp, 0, (int)(pixel / W), (int)npix, &fp);
     if (st) return st;
     if (!log || cap <= 0 || !n_events || !out3) return set_err(ctx, RT_ERR_ARG, "bad log buffer");
     if (traversal == RT_TRAVERSAL_FAST && !ctx->hs.fast_ok) traversal = RT_TRAVERSAL_REF;
-    fp.max_bounce = max_bounce;
+    fp.max_bounce = max_bounce;   // (this entry point has never bounded it: check_frame got 0)
     fp.sun_skip = 0;   // the event log records every ray the reference traces, with its closest hit
     fp.sun_any = 0;
     Device& d = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     const size_t obytes = (size_t)fp.nloc * 3 * sizeof(float);
     const size_t lbytes = (size_t)cap * 16 * sizeof(float);
-    HIP_OR_RET(ctx, ensure(d.scratch_a, obytes + lbytes + 16));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, obytes + lbytes + 16));
     float* dout = (float*)d.scratch_a.p;
     fp.log_buf = dout + fp.nloc * 3;
     fp.log_count = (int32_t*)(fp.log_buf + (size_t)cap * 16);

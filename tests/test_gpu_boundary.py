@@ -133,6 +133,46 @@ def test_multi_device_launcher_deinterleaves_rows(case, slots):
         multi.close()
 
 
+def test_a_slot_without_rows_and_a_partial_row():
+    """Three slots of one device on 8 + 5 pixels in rows of 8: slot 0 holds a full row, slot 1 the partial
+    one, slot 2 nothing.  Every host form that gathers or scatters rows gives the one-slot context's bits."""
+    sc, cam, env, _, _, mb, ibl = W.PARITY_CASES["cornell_64_s4"].with_size(8, 2, 4).inputs()
+    cam = cam.copy()
+    cam[3] -= 30.0   # (looks down from the ceiling these two rows would show: 12 of the 13 pixels are lit at 4 spp)
+    npix = 8 + 5
+    mask = (np.arange(npix) % 3 == 0).astype(np.uint8)
+    got = {}
+    for slots in (1, 3):
+        c = _native.Context(device_ids=[0] * slots)
+        try:
+            c.set_env(ibl)
+            c.set_scene(sc.V_p, sc.V_n, sc.V_uv, sc.faceData, sc.materialData, sc.BVH.exportArray)
+            r = got[slots] = {}
+            r["render"] = c.render(cam, env, npix, 4, mb, np.full(3 * npix, -1.0, np.float32))
+            r["rgb8"] = c.render_rgb8(cam, env, npix, 4, mb, gamma=True)
+            c.accum_begin(cam, env, npix, mb)
+            r["add1"] = c.accum_add(1, np.full(3 * npix, -1.0, np.float32))
+            r["add4"] = c.accum_add(3, np.full(3 * npix, -1.0, np.float32))
+            r["read"] = c.accum_read(np.full(3 * npix, -1.0, np.float32))
+            c.accum_select_mask(mask)
+            r["selection"] = c.accum_selection().copy()
+            r["selected"] = c.accum_add_selected(2, np.full(3 * npix, -1.0, np.float32))
+            r["samples"] = c.accum_sample_map().copy()
+            r["guides"] = c.accum_guides().copy()
+            c.accum_end()
+        finally:
+            c.close()
+    one, three = got[1], got[3]
+    np.testing.assert_array_equal(one["add4"], one["render"])   # (4 spp either way)
+    assert len(np.unique(one["render"])) > 8 and len(np.unique(one["rgb8"])) > 3 and one["guides"].any()
+    np.testing.assert_array_equal(one["selection"], mask)
+    np.testing.assert_array_equal(one["samples"], np.where(mask, 6, 4))
+    for name in one:
+        a, b = one[name], three[name]
+        assert a.dtype == b.dtype and a.shape == b.shape, name
+        np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8), err_msg=name)
+
+
 RCCL_ONE_RANK = r'''
 import os, sys
 sys.path.insert(0, sys.argv[1])
