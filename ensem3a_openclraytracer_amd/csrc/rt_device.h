@@ -630,12 +630,10 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             const float t[6] = {x0, x1, y0, y1, z0, z1};
             const float mn[3] = {fminf(x0, x1), fminf(y0, y1), fminf(z0, z1)};
             const float mx[3] = {fmaxf(x0, x1), fmaxf(y0, y1), fmaxf(z0, z1)};
-            // the records of the faces -x +x -y +y -z +z (an absent face: -1 -1, skipped by the wave-uniform
-            // branch around its enqueue: the compiler sinks each face's test -- v_max, v_min, v_max3, v_min3,
-            // v_cmp -- to its one use there, so the pass mask goes from vcc straight into the enqueue).  A
-            // branch of its own around each test, ahead of the enqueues, measured slower on C2's five faces
-            // (r15, DESIGN.md 5.2: 6.16-6.18 against 6.02-6.03 ms): six more compare-and-branch pairs, and
-            // every pass mask is kept in an SGPR pair until its enqueue
+            // the records of the faces -x +x -y +y -z +z (an absent face: -1 -1).  All six tests -- v_max, v_min,
+            // v_max3, v_min3, v_cmp each -- run without a branch, the absent positions' too: their pass masks feed
+            // the one queue step below.  (r15 had a branch around each face's enqueue, into which the compiler sank
+            // the face's test; a branch of its own around each test measured slower then)
             const int q[12] = {__float_as_int(fx.x), __float_as_int(fx.y), __float_as_int(fx.z), __float_as_int(fx.w),
                                __float_as_int(fy.x), __float_as_int(fy.y), __float_as_int(fy.z), __float_as_int(fy.w),
                                __float_as_int(fz.x), __float_as_int(fz.y), __float_as_int(fz.z), __float_as_int(fz.w)};
@@ -648,13 +646,58 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 // box_hit() with the shell's floor for its 0.0f (DevScene::near_floor, option "brute_near": kNearFloor
                 // where the packer found every face near-safe, else 0.0f itself): a pass with tx below the floor is
                 // one whose triangles return k <= 0.0001f.  The scalar is spilled to a lane and read
-                // back at each test, which the compiler sinks to its enqueue; folding the floor into two of the axis
-                // minima once per ray instead measured the same frame time and cost the adds' kernels a VGPR (r17)
+                // back for the tests; folding the floor into two of the axis minima once per ray instead measured the
+                // same frame time and cost the adds' kernels a VGPR (r17)
                 pass[f] = fmaxf(tn, nearf) <= fminf(tx, cull);
             }
+            // One queue step for all the faces (r18).  A ray that starts inside the shell leaves through one face, and
+            // with the floor the face it starts on does not pass: a lane passes at most one of the six tests, except
+            // on an edge, on a corner, from outside or with a non-finite ray.  When the six pass masks are disjoint
+            // (their popcounts sum to their union's), every passing lane takes the records of its own face -- a
+            // select chain over one scalar word per face, first record | second << 16; -1 -1 of an absent face gives
+            // ~0u, a missing second record 0xffff above a first one < 0xffff -- and the wave queues them in one step:
+            // the first records at the rank among the passing lanes, the second ones behind them at the rank among
+            // the lanes that have one, as run_items does.  The ring's bound is enqueue's: fewer than nact (<= 64) pairs
+            // are queued before the step and a lane adds at most 2, 128 in all, under the ring's 256.  Otherwise the
+            // faces are queued one by one as before.  The ring's order differs between the two paths, and with it
+            // when batches run and which bk a later cull sees: bestk is an atomic minimum over (k, record) keys and
+            // a cull changes no hit.  Measured and not kept (r18): the records from a table in LDS
+            // indexed by a face number (the same time), absent faces masked out of the check (slower, or the same
+            // when done only after the check fails)
+            unsigned long long many = 0;
+            int npass = 0;
 #pragma unroll
-            for (int f = 0; f < 6; ++f)
-                if (q[2 * f] >= 0) enqueue(pass[f], (unsigned)q[2 * f], q[2 * f + 1]);
+            for (int f = 0; f < 6; ++f) {
+                const unsigned long long mf = __ballot(pass[f]);
+                many |= mf;
+                npass += __popcll(mf);
+            }
+            if (npass == __popcll(many)) {
+                unsigned pk = ~0u;
+#pragma unroll
+                for (int f = 0; f < 6; ++f) pk = pass[f] ? ((unsigned)q[2 * f] | ((unsigned)q[2 * f + 1] << 16)) : pk;
+                const bool p1 = pk != ~0u, p2 = pk < 0xffff0000u;
+                const unsigned long long m1 = __ballot(p1);
+                if (m1 != 0) {
+                    const unsigned long long m2 = __ballot(p2);
+                    const unsigned n1 = (unsigned)__popcll(m1);
+                    if (COUNT && p1) c.tris += p2 ? 2 : 1;
+                    // no exec-mask change, as in enqueue: a lane that queues nothing writes to its dummy slot
+                    const unsigned r1 = lane_prefix(m1, tail), r2 = lane_prefix(m2, tail + n1);
+                    ring[p1 ? (r1 & (BRUTE_RING - 1)) : BRUTE_RING + lane] = (tl << 16) | (pk & 0xffffu);
+                    ring[p2 ? (r2 & (BRUTE_RING - 1)) : BRUTE_RING + lane] = (tl << 16) | (pk >> 16);
+                    tail += n1 + (unsigned)__popcll(m2);
+                    wave_lds_sync();
+                    if ((int)(tail - head) >= nact) {
+                        do run_batch(nact); while ((int)(tail - head) >= nact);
+                        bk = __uint_as_float((unsigned)(bestk[tl] >> 32));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int f = 0; f < 6; ++f)
+                    if (q[2 * f] >= 0) enqueue(pass[f], (unsigned)q[2 * f], q[2 * f + 1]);
+            }
             sb = ConstF4{sh.p + kShellRecF};
             ns = __float_as_int(h1.z);
         }
