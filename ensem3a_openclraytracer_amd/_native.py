@@ -39,7 +39,8 @@ EXPORTED = (
     "rt_trace", "rt_trace_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
-    "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_slices",
+    "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
+    "rt_debug_brute_slices",
     "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
@@ -49,7 +50,7 @@ EXPORTED = (
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
              "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout",
-             "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near")
+             "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -191,6 +192,8 @@ def lib():
                                             _c_p, _i64, _c_p]),
             "rt_debug_brute_near": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32,
                                            _c_p, _i64, _c_p, _c_p]),
+            "rt_debug_brute_quad": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32,
+                                           _i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
             "rt_debug_brute_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _c_p]),
             "rt_debug_last_slices": (_i32, []),
             "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
@@ -680,7 +683,7 @@ def brute_clusters(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, lay
     return slots.reshape(-1, 8), rows.reshape(-1, 8), int(info[1])
 
 
-SHELL_REC_FLOATS = 20   # rt_debug_brute_shell's record: the box, two counts, two records for each of six faces
+SHELL_REC_FLOATS = 76   # rt_debug_brute_shell's record: the box, two counts, two records for each of six faces, seven rows of 8
 
 
 def brute_shell(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: int = -1, layout: int = RT_BVH_SAH):
@@ -704,7 +707,8 @@ def brute_shell(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell:
     if st != 0:
         raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
     ints = rec[:SHELL_REC_FLOATS].view(np.int32)
-    return dict(box=rec[:6].copy(), nrest=int(ints[6]), nfaces=int(ints[7]), faces=ints[8:20].reshape(6, 2).copy(),
+    # (the face count's word carries the number of split faces above bit 8, option "brute_quad")
+    return dict(box=rec[:6].copy(), nrest=int(ints[6]), nfaces=int(ints[7]) & 0xff, faces=ints[8:20].reshape(6, 2).copy(),
                 rest=rec[SHELL_REC_FLOATS:].reshape(-1, 8).copy())
 
 
@@ -730,6 +734,28 @@ def brute_near(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: 
     if st != 0:
         raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
     return flags.astype(bool), np.float32(floor[0]), int(info[1])
+
+
+QUAD_BAND, QUAD_GRAZE, QUAD_DIR_MAX = np.float32(2.0 ** -8), np.float32(2.0 ** -6), np.float32(2.0)   # rt_layout.h
+
+
+def brute_quad(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: int = -1, quad: int = -1,
+               layout: int = RT_BVH_SAH):
+    """rt_debug_brute_quad (include/rt_debug.h), on the host alone: a dict of ``split`` and ``side`` (bool [6], per
+    face position -x +x -y +y -z +z), ``lines`` (float32 [6, 4]: A.xyz gamma), ``words`` (uint32 [6, 3]: the packed
+    records both / sigma >= 0 / sigma < 0), ``recs`` (float32 [6, 2, 3, 3]: p0, e1, e2 of the two records), ``guard`` (kQuadBand, kQuadGraze, kQuadDirMax), ``nfaces``, ``nsplit``."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    flags, lines, words = np.zeros(6, np.int32), np.zeros(24, np.float32), np.zeros(18, np.int32)
+    recs, guard, info = np.zeros(108, np.float32), np.zeros(3, np.float32), np.zeros(2, np.int64)
+    st = host_lib().rt_debug_brute_quad(ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size,
+                                        ptr(b), b.size, int(layout), int(cluster), int(shell), int(quad),
+                                        flags.ctypes.data, lines.ctypes.data, words.ctypes.data, recs.ctypes.data,
+                                        guard.ctypes.data,
+                                        info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, host_lib().rt_scene_last_error().decode(errors="replace"))
+    return dict(split=(flags & 1).astype(bool), side=((flags >> 1) & 1).astype(bool), lines=lines.reshape(6, 4),
+                words=words.view(np.uint32).reshape(6, 3), recs=recs.reshape(6, 2, 3, 3), guard=guard, nfaces=int(info[0]), nsplit=int(info[1]))
 
 
 def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: int = -1):
@@ -768,7 +794,7 @@ def last_refill():
 
 
 LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide", "brute", "ts", "acc",
-                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near")
+                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near", "quad")
 BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
 BRUTE_REFILL = 8
 
@@ -776,7 +802,7 @@ BRUTE_REFILL = 8
 def last_launch() -> dict:
     """rt_debug_last_launch (include/rt_debug.h): the kernel key of the last render launch and the team sizes,
     slice word, refill threshold, grid and LDS bytes its kernel got, whether it walked a shell and whether that
-    shell's face tests had a non-zero floor (option "brute_near"), by name
+    shell's face tests had a non-zero floor (option "brute_near") and its record split walls (option "brute_quad"), by name
     (``LAUNCH_FIELDS``)."""
     out = np.zeros(len(LAUNCH_FIELDS), np.int32)
     st = lib().rt_debug_last_launch(out.ctypes.data)

@@ -137,6 +137,7 @@ struct rt_ctx {
     int brute_cluster = -1;  // brute force: clustered leaf boxes (0 off, 1 force, -1 auto; option "brute_cluster")
     int brute_shell = -1;    // ... and the shell among their single slots (0 off, 1 force, -1 auto; option "brute_shell")
     int brute_near = -1;     // ... whose face tests take the packer's floor (0 off, -1 or 1 auto; option "brute_near")
+    int brute_quad = -1;     // ... and whose split walls queue one record (0 off, -1 or 1 auto; option "brute_quad")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
     int walk_team = 0;  // tree walk (BVH2 item steps): lanes per pixel walking each ray together, 0 = auto
@@ -327,7 +328,7 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.ncluster = ctx->hs.ncluster;
     s.ncslot = (int32_t)(ctx->hs.brute_cbox.size() / 8);
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
-    s.cluster_auto = ctx->brute_cluster < 0 ? 1 : 0;
+    s.host_flags = (ctx->brute_cluster < 0 ? rt::kHostClusterAuto : 0) | (ctx->hs.nquad > 0 ? rt::kHostQuad : 0);
     s.nsingle = ctx->hs.nsingle;
     s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
     s.near_floor = s.shell && ctx->brute_near != 0 ? ctx->hs.shell_floor : 0.0f;
@@ -415,14 +416,14 @@ int slot_of(rt_ctx* ctx, int device_index, Device** d, const char* what = "devic
     return RT_OK;
 }
 
-// The options that pack the scene again ("bvh", "brute_max", "brute_cluster", "brute_shell"): the FAST layout of
+// The options that pack the scene again ("bvh", "brute_max", "brute_cluster", "brute_shell", "brute_quad"): the FAST layout of
 // the current scene from the values as they are now, on every slot.  Without a scene there is nothing to do.
 int repack_scene(rt_ctx* ctx) {
     if (!ctx->have_scene) return RT_OK;
     HostScene& hs = ctx->hs;
     std::string why;
     rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster,
-                     ctx->brute_shell, why);
+                     ctx->brute_shell, ctx->brute_quad, why);
     for (auto& d : ctx->devs) {
         const int st = upload_fast(ctx, d, hs);
         if (st) return st;
@@ -474,6 +475,8 @@ const std::vector<Option>& options() {
         // no repack and no upload: the packer decides where the floor is safe whatever the option, and the floor
         // reaches the kernels in DevScene, made for every launch (dev_scene); the frame is the same either way
         {"brute_near", &rt_ctx::brute_near, range(-1, 1), "brute_near must be -1 (auto), 0 (off) or 1 (auto)", none},
+        // the lines and the enable ride in the shell's record (no DevScene field): packed and uploaded again
+        {"brute_quad", &rt_ctx::brute_quad, range(-1, 1), "brute_quad must be -1 (auto), 0 (off) or 1 (auto)", repack},
         {"bvh", &rt_ctx::bvh_layout, range(RT_BVH_REFERENCE, RT_BVH_SAH), "bvh must be 0 (reference tree) or 1 (sah)", repack},
         {"brute_cluster", &rt_ctx::brute_cluster, range(-1, 1), "brute_cluster must be -1 (auto), 0 (off) or 1 (force)", repack},
         {"brute_shell", &rt_ctx::brute_shell, range(-1, 1), "brute_shell must be -1 (auto), 0 (off) or 1 (force)", repack},
@@ -586,7 +589,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     HostScene hs;
     std::string msg, why;
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, ctx->bvh_layout,
-                                     ctx->brute_max, ctx->brute_cluster, ctx->brute_shell, msg, why);
+                                     ctx->brute_max, ctx->brute_cluster, ctx->brute_shell, ctx->brute_quad, msg, why);
     if (rc != RT_OK) return set_err(ctx, rc, "%s", msg.c_str());
     invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
@@ -1832,14 +1835,14 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 
 int rt_debug_last_slices(void) { return rt::last_launch().slices; }
 
-int rt_debug_last_launch(int32_t out[19]) {
+int rt_debug_last_launch(int32_t out[20]) {
     if (!out) return RT_ERR_ARG;
     const rt::LaunchNote n = rt::last_launch();
     const rt::KernelKey& k = n.key;
-    const int64_t v[19] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
+    const int64_t v[20] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
                            k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds,
-                           n.shell, n.near};
-    for (int i = 0; i < 19; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+                           n.shell, n.near, n.quad};
+    for (int i = 0; i < 20; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
     return RT_OK;
 }
 

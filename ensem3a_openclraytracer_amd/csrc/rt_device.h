@@ -461,6 +461,38 @@ __device__ __forceinline__ float near_floor_of(const DevScene& S, int g) {
     return g < 64 && ((m >> (g & 31)) & 1u) ? kNearFloor : 0.0f;
 }
 
+// fmaxf(fmaxf(a, b), c) and fminf(fminf(a, b), c) as the one instruction each is (a NaN operand is dropped, as
+// fmaxf and fminf drop it).  Written out because the compiler, which cannot see across basic blocks that slab
+// minima and maxima are canonical, otherwise spends a v_max x, x on each operand first (r19: 6 VALU for the two)
+__device__ __forceinline__ float max3_f32(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ float min3_f32(float a, float b, float c) {
+    float r;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// The one queue step's choice between the two records of a split wall (option "brute_quad", rt_layout.h kQuadBand;
+// DESIGN.md 4.2 has the rule and the proof).  ln, wd: the row of the lane's face in the shell's record -- the
+// line A.xyz gamma | the packed records: both, the one on sigma >= 0, the one on sigma < 0 (~0u for "no face"; a
+// face that is not split has a zero line and three equal words).  tin, T: the shell box's entry and exit distance,
+// the largest of the axes' slab minima and the smallest of their maxima (max3_f32, min3_f32); da: the
+// direction's component along the face's axis.  For a lane that passes its face's test the box's exit distance
+// is that face's own plane distance, bit for bit, unless a NaN was dropped on the way, and
+// every NaN or infinity in o, d or the distances makes sigma~ a NaN or fails a comparison below: each is written
+// as a positive condition.  P~ decides nothing but which record is queued, so fmaf may contract it.
+__device__ __forceinline__ unsigned quad_pick(float4 ln, float4 wd, rtm_f3 o, rtm_f3 d, float tin, float T, float da) {
+    const float sg = fmaf(ln.x, fmaf(T, d.x, o.x), fmaf(ln.y, fmaf(T, d.y, o.y), fmaf(ln.z, fmaf(T, d.z, o.z), ln.w)));
+    const float dm = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+    // (& for &&: one straight run of compares, no branch around the table's reads)
+    const bool sure = (tin <= 0.0f) & (T >= 0.0f) & (fabsf(da) >= kQuadGraze * dm) & (dm <= kQuadDirMax) &
+                      (fabsf(sg) >= kQuadBand);
+    return __float_as_uint(sure ? (sg >= 0.0f ? wd.y : wd.z) : wd.x);
+}
+
 // a width of the lock-step walk's pieces, as a type (trace_brute_compact)
 template <int N> struct IntC { static constexpr int value = N; };
 static_assert(kBoxGroup == 1 || kBoxGroup == 2 || kBoxGroup == 4 || kBoxGroup == 8, "the lock-step tail is cut into powers of two");
@@ -552,6 +584,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
     // the box and its one or two records), all their slab tests run back to back, then the passes are queued
     // (culling uses the best hit as of the group's start: conservative).  nreal: the real slots of the array
     // (instrumented build)
+    unsigned cq_pk = 0;   // (instrumented lock-step loop)
     auto group = [&](auto wc, const ConstF4 cb, int g0, int nreal) __attribute__((always_inline)) {
         constexpr int W = decltype(wc)::value;
         float4 bx[2 * W];
@@ -583,7 +616,16 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 count_wave(c.wave_trav); c.nodes++;
                 if (qb >= 0) { count_wave(c.wave_trav); c.nodes++; }
             }
-            enqueue(pass[j], (unsigned)qa, qb);
+            if constexpr (COUNT && !CLU) {
+                // a split wall of the shell, when the product kernel's one queue step would run (cq_pk: the lane's
+                // word from quad_pick, below): the lanes that are sure queue the one record
+                const unsigned keep = cq_pk & 0xffffu;
+                const bool one = pass[j] && qb >= 0 && cq_pk >= 0xffff0000u && (keep == (unsigned)qa || keep == (unsigned)qb);
+                enqueue(pass[j] && !one, (unsigned)qa, qb);
+                enqueue(one, keep, -1);
+            } else {
+                enqueue(pass[j], (unsigned)qa, qb);
+            }
         }
     };
     // slots [gb, ge) of cb in whole groups of kBoxGroup, the padding slots of the last one included (the
@@ -623,6 +665,8 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         if (S.shell) {
             const ConstF4 sh{cb.p + 4 * S.shell};
             const float4 h0 = sgpr4(sh[0]), h1 = sgpr4(sh[1]), fx = sgpr4(sh[2]), fy = sgpr4(sh[3]), fz = sgpr4(sh[4]);
+            // split walls in the record (above the face count; 0: option "brute_quad" is off or nothing to split)
+            const int nquad = __float_as_int(h1.w) >> 8;
             const float cull = bk * CULL_MARGIN, nearf = S.near_floor;
             const float x0 = (h0.x - o.x) * ix, x1 = (h0.y - o.x) * ix;
             const float y0 = (h0.z - o.y) * iy, y1 = (h0.w - o.y) * iy;
@@ -654,8 +698,9 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             // with the floor the face it starts on does not pass: a lane passes at most one of the six tests, except
             // on an edge, on a corner, from outside or with a non-finite ray.  When the six pass masks are disjoint
             // (their popcounts sum to their union's), every passing lane takes the records of its own face -- a
-            // select chain over one scalar word per face, first record | second << 16; -1 -1 of an absent face gives
-            // ~0u, a missing second record 0xffff above a first one < 0xffff -- and the wave queues them in one step:
+            // word per face, first record | second << 16, from the face's row of the record; -1 -1 of an absent face
+            // gives ~0u, a missing second record 0xffff above a first one < 0xffff, and so does the record quad_pick
+            // leaves out of a split wall -- and the wave queues them in one step:
             // the first records at the rank among the passing lanes, the second ones behind them at the rank among
             // the lanes that have one, as run_items does.  The ring's bound is enqueue's: fewer than nact (<= 64) pairs
             // are queued before the step and a lane adds at most 2, 128 in all, under the ring's 256.  Otherwise the
@@ -673,9 +718,19 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 npass += __popcll(mf);
             }
             if (npass == __popcll(many)) {
-                unsigned pk = ~0u;
+                // the lane's face's row of the shell's table (LDS, behind the slots' copy; the last row: no face)
+                // -- the select chain picks the row, not the word -- and quad_pick's choice among its words (r19)
+                int row = 2 * 6;
 #pragma unroll
-                for (int f = 0; f < 6; ++f) pk = pass[f] ? ((unsigned)q[2 * f] | ((unsigned)q[2 * f + 1] << 16)) : pk;
+                for (int f = 0; f < 6; ++f) row = pass[f] ? 2 * f : row;
+                const float4* rw = boxrec + S.shell + row;
+                unsigned pk;
+                if (nquad) {   // (wave-uniform: the record's count of split walls)
+                    const float da = (pass[0] || pass[1]) ? d.x : (pass[2] || pass[3]) ? d.y : d.z;
+                    pk = quad_pick(rw[0], rw[1], o, d, max3_f32(mn[0], mn[1], mn[2]), min3_f32(mx[0], mx[1], mx[2]), da);
+                } else {
+                    pk = __float_as_uint(rw[1].x);
+                }
                 const bool p1 = pk != ~0u, p2 = pk < 0xffff0000u;
                 const unsigned long long m1 = __ballot(p1);
                 if (m1 != 0) {
@@ -760,6 +815,40 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         }
         while (itail != ihead) run_items(min((int)(itail - ihead), nact));
     } else if (ts == 1) {
+        if constexpr (COUNT) {
+            // the instrumented loop counts the pairs the clustered product kernel queues (option "brute_quad"): the
+            // shell's six face tests as that kernel runs them, its check that no lane passes two, and quad_pick on
+            // the lane's face's row, read from the record itself
+            if (S.shell) {
+                const ConstF4 sh{as_const(S.brute_cbox).p + 4 * S.shell};
+                const float4 h0 = sgpr4(sh[0]), h1 = sgpr4(sh[1]);
+                const float cull = bk * CULL_MARGIN, nearf = S.near_floor;
+                const float x0 = (h0.x - o.x) * ix, x1 = (h0.y - o.x) * ix;
+                const float y0 = (h0.z - o.y) * iy, y1 = (h0.w - o.y) * iy;
+                const float z0 = (h1.x - o.z) * iz, z1 = (h1.y - o.z) * iz;
+                const float t[6] = {x0, x1, y0, y1, z0, z1};
+                const float mn[3] = {fminf(x0, x1), fminf(y0, y1), fminf(z0, z1)};
+                const float mx[3] = {fmaxf(x0, x1), fmaxf(y0, y1), fmaxf(z0, z1)};
+                unsigned long long many = 0;
+                int npass = 0, row = 2 * 6;
+                bool pass[6];
+                for (int f = 0; f < 6; ++f) {
+                    const int a = f >> 1;
+                    const float tn = fmaxf(fmaxf(a == 0 ? t[f] : mn[0], a == 1 ? t[f] : mn[1]), a == 2 ? t[f] : mn[2]);
+                    const float tx = fminf(fminf(a == 0 ? t[f] : mx[0], a == 1 ? t[f] : mx[1]), a == 2 ? t[f] : mx[2]);
+                    pass[f] = fmaxf(tn, nearf) <= fminf(tx, cull);
+                    const unsigned long long mf = __ballot(pass[f]);
+                    many |= mf;
+                    npass += __popcll(mf);
+                    row = pass[f] ? 2 * f : row;
+                }
+                if (npass == __popcll(many)) {
+                    const float4* rw = S.brute_cbox + S.shell + kShellRowF4 + row;
+                    const float da = (pass[0] || pass[1]) ? d.x : (pass[2] || pass[3]) ? d.y : d.z;
+                    cq_pk = quad_pick(rw[0], rw[1], o, d, max3_f32(mn[0], mn[1], mn[2]), min3_f32(mx[0], mx[1], mx[2]), da);
+                }
+            }
+        }
         lockstep_padded(as_const(S.brute_box), 0, S.nbox);
     } else {
         // box g = gg * ts + sub of each round (LDS copy of brute_box at boxrec); its second record, when
@@ -857,7 +946,8 @@ inline size_t stack_lds_bytes(const DevScene& sc, int traversal, int block) {
 // ... of the brute-force kernels (BRUTE_ != 0), which stage the scene: records, boxes, shading, materials, clusters
 inline size_t brute_lds_bytes(const DevScene& sc, int block) {
     return (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.nbox * 32 +
-           (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32;
+           (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32 +
+           (sc.shell ? (size_t)kShellRows * 32 : 0);
 }
 // ... and what the SMEM walks stage behind their stack: the BVH2 nodes and the triangles
 inline size_t staged_scene_bytes(const DevScene& sc) {

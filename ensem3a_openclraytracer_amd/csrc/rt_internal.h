@@ -10,6 +10,9 @@
 namespace rt {
 
 // Device view of one uploaded scene (all pointers are device pointers).
+// bits of DevScene::host_flags
+constexpr int32_t kHostClusterAuto = 1;   // option "brute_cluster" is -1: only tiles of at least a pixel per resident lane are clustered
+constexpr int32_t kHostQuad = 2;          // the shell's record has split faces (option "brute_quad"; rt_debug_last_launch)
 struct DevScene {
     // FAST traversal: BVH2 nodes holding both child boxes, 4 x float4 each:
     //   [0] = c0.min.x, c0.max.x, c0.min.y, c0.max.y
@@ -91,7 +94,9 @@ struct DevScene {
     const float4* brute_cbox;
     const float4* brute_crow;
     int32_t ncluster, ncslot, nsingle4;
-    int32_t cluster_auto;   // option "brute_cluster" is -1: launch_pick clusters only tiles of at least a pixel per resident lane
+    // host-side flags (launch_pick and its note; no kernel reads them): kHostClusterAuto, kHostQuad below.  One word
+    // where the structure had the "brute_cluster is auto" flag, so no kernel's arguments move
+    int32_t host_flags;
     // the real single slots at the head of brute_cbox.  The clustered loop tests slots [0, nsingle) and, where a
     // cluster runs lock-step, its `count` boxes in whole groups of kBoxGroup and then the last 1..3 alone: the
     // padding slots stay in memory -- a group load never leaves the buffer, an item's slot index is a shift and
@@ -340,6 +345,7 @@ struct LaunchNote {
     size_t lds;
     int shell;   // the kernel walks the scene's shell (the clustered loop, DevScene::shell != 0)
     int near;    // ... with a non-zero floor in its face tests (DevScene::near_floor != 0)
+    int quad;    // ... and split faces in its record (option "brute_quad")
 };
 void note_launch(const LaunchNote& n);
 LaunchNote last_launch();

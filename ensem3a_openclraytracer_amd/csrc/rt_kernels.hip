@@ -109,6 +109,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         if (BRUTE == 3) {   // the clustered loop's item tests read their slots here
             float4* lc = reinterpret_cast<float4*>(lm + kMatF * S.nmat);
             for (int q = threadIdx.x; q < 2 * S.ncslot; q += B) lc[q] = S.brute_cbox[q];
+            // ... and the shell's rows behind them (rt_layout.h kShellRows; trace_brute_compact's one queue step
+            // reads a lane's face's row), at boxrec + S.shell
+            if (S.shell)
+                for (int q = threadIdx.x; q < 2 * kShellRows; q += B) lc[S.shell + q] = S.brute_cbox[S.shell + kShellRowF4 + q];
             boxrec = lc;
         }
         __syncthreads();
@@ -1329,7 +1333,7 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     // auto: only tiles with at least one pixel per resident lane.  Measured on C2: the whole
     // frame (3.2 pixels per lane) 7.29 -> 7.02 ms, the 1/8 tile (0.4 per lane: half-empty waves that wait on
     // the LDS round trips of the item batches instead of on VALU issue) 2.14 -> 2.23 ms
-    if (brute && product && sc.ncluster > 0 && !(sc.cluster_auto && fp.nloc < resident(0) * block)) k.brute = 3;
+    if (brute && product && sc.ncluster > 0 && !((sc.host_flags & kHostClusterAuto) && fp.nloc < resident(0) * block)) k.brute = 3;
     const int64_t lanes = resident(fp.max_waves) * block;
     if (e != hipSuccess) return e;
     FrameParams f = fp;
@@ -1376,7 +1380,8 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     if (e == hipSuccess) e = setup_work_block(f, d_work, stream, &lc);
     if (e != hipSuccess) return e;
     const int shell = (k.brute & 3) == 3 && sc.shell != 0;
-    note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f});
+    note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f,
+                 shell && (sc.host_flags & kHostQuad) != 0});
     DevScene a0 = sc;
     void* args[] = {&a0, &f, &d_out, &d_counts, &d_work, &lc};
     return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);

@@ -39,14 +39,37 @@ constexpr double kClusterGain = 0.75;
 // boxes, equal at n = nact / kappa = 0.53 nact
 constexpr int kClusterLockNum = 4;
 // The shell among a clustered scene's single slots (scene_pack.cpp build_shell, option "brute_shell"): its record
-// is kShellRecF floats (5 float4), the remaining singles' slots follow it.  auto takes a shell from kShellMinFaces
+// is kShellRecF floats (5 float4 and the rows below), the remaining singles' slots follow it.  auto takes a shell from kShellMinFaces
 // faces: the smallest count at which the shell piece issues fewer VALU + SALU instructions than as many single
 // tests, counted in the built gfx950 kernel: n single tests are 23 n VALU; the shell piece is 18
 // shared VALU (6 subtracts, 6 multiplies, 3 min / max pairs), up to 8 canonicalising v_max, 5 VALU per face (3
 // for the second of a -z +z pair) and 12 SALU (a compare and a branch per face position) -- at most 48 against 46
 // for two faces, at most 53 against 69 for three
-constexpr int kShellRecF = 20;
+// Behind those 5 float4 the record carries kShellRows rows of 2 float4, one per face position -x +x -y +y -z +z and
+// a last one for "no face" (option "brute_quad", scene_pack.cpp quad_split): the face's line A.x A.y A.z gamma |
+// its packed records first | second << 16 (both, the one on sigma >= 0, the one on sigma < 0; ~0u: none), flags
+// (bit 0 split, bit 1 the first record is on the positive side).  A face that is not split has a zero line.  The
+// record's face count carries the number of split faces above bit 8 (0: the rule is off).
+constexpr int kShellRows = 7;
+constexpr int kShellRowF4 = 5;                     // where the rows start in the record, in float4
+constexpr int kShellRecF = 20 + 8 * kShellRows;
 constexpr int kShellMinFaces = 3;
+// The one queue step's choice between a split wall's two records (option "brute_quad"; DESIGN.md 4.2 has the proof).
+// A lane is sure of its side sigma~ = A . (o + T d) + gamma of the wall's diagonal, and queues that side's record
+// alone, when the origin lies in the shell's box, kQuadGraze max|d| <= |d_a| for the wall's axis a, max|d| <=
+// kQuadDirMax and |sigma~| >= kQuadBand.  The packer splits a wall only when kQuadBand is at least kQuadSafety
+// times the wall's own error bound (the classifier's and Moller-Trumbore's on the dropped record, plus kQuadSlack
+// for the packer's double arithmetic, scaled by the triangles' height ratio, at most kQuadRatio), its records cancel
+// by at most kQuadKappa and every component lies within 2^+-kQuadExp.  Cornell's walls' bound is 2^-17.6: 8 times that
+// is 2^6 below the band, which leaves 1 - 2^-7 of a wall's width outside it.  Not tuned to any frame time
+constexpr float kQuadBand = 0x1p-8f;
+constexpr float kQuadGraze = 0x1p-6f;
+constexpr float kQuadDirMax = 2.0f;
+constexpr double kQuadSafety = 8.0;
+constexpr double kQuadSlack = 0x1p-20;
+constexpr double kQuadRatio = 4.0;
+constexpr double kQuadKappa = 4.0;
+constexpr int kQuadExp = 24;
 // The floor of the shell's face tests (option "brute_near", DevScene::near_floor; DESIGN.md 4.2 has the proof).  A
 // ray that starts on a wall passes that wall's flat box at a plane distance t of 0 to a few 1e-7, and the wall's
 // triangles then return k = t up to rounding, which the k > 0.0001f of the hit condition throws away.  A face test

@@ -540,6 +540,117 @@ bool near_safe(const HostScene& hs, const float* b) {
     return true;
 }
 
+// A split wall (option "brute_quad"; rule, bound and proof: DESIGN.md 4.2).  Face slot b of shell box S (6 bounds)
+// is split when it is near-safe, lists two records whose vertices p0, p0 + e1, p0 + e2 are exact in double, every
+// component within 2^+-kQuadExp, cancellation at most kQuadKappa, and there is an edge coordinate l1 (u, v or
+// 1 - u - v) of the first record and one l2 of the second with l1 = s sigma / r1 and l2 = -s sigma / r2 to within
+// kQuadSlack at the four corners of the face -- so over all of it, the functions being affine -- where sigma(P) =
+// A . P + gamma is the line with float coefficients the kernel evaluates, s = +-1, and r1, r2 in [1, kQuadRatio]
+// are the triangles' heights over the line in units of the smaller one.  The first non-zero component of A is
+// positive; side = the first record lies on sigma >= 0.  Last, kQuadBand must be kQuadSafety times the wall's error
+// bound (quad_bound below, restated in tests/test_brute_quad.py).  Every doubt: not split.
+struct QuadLine { float A[3] = {0, 0, 0}; float gamma = 0; int side = 0; };
+bool quad_split(const HostScene& hs, const float* b, const float* S, QuadLine& out) {
+    if (!near_safe(hs, b)) return false;
+    int32_t q[2];
+    std::memcpy(q, b + 6, 8);
+    if (q[1] < 0) return false;
+    int a = 0;
+    for (int k = 0; k < 3; ++k) if (b[2 * k] == b[2 * k + 1]) a = k;
+    const int ax[2] = {(a + 1) % 3, (a + 2) % 3};
+    const double lo = std::ldexp(1.0, -rt::kQuadExp), hi = std::ldexp(1.0, rt::kQuadExp);
+    auto in_range = [&](double v) { return v == 0.0 || (std::fabs(v) >= lo && std::fabs(v) <= hi); };
+    for (int k = 0; k < 6; ++k) if (!in_range(S[k])) return false;
+    const double eps = std::ldexp(1.0, -24) * (1.0 + std::ldexp(1.0, -10));
+    double W[2], Cm[2], corner[4][2];
+    for (int j = 0; j < 2; ++j) {
+        W[j] = (double)S[2 * ax[j] + 1] - (double)S[2 * ax[j]];
+        Cm[j] = std::max(std::fabs((double)S[2 * ax[j]]), std::fabs((double)S[2 * ax[j] + 1]));
+    }
+    for (int c = 0; c < 4; ++c) {
+        corner[c][0] = S[2 * ax[0] + (c & 1)];
+        corner[c][1] = S[2 * ax[1] + (c >> 1)];
+    }
+    // the two triangles' edge coordinates as affine functions g0 P[0] + g1 P[1] + c of the in-plane point, their
+    // bounds over the face and Moller-Trumbore's error on each (quad_bound)
+    struct Coord { double g[2], c, err; };
+    Coord L[2][3];
+    double V[2][3][2];
+    for (int t = 0; t < 2; ++t) {
+        const float* r = hs.brute.data() + 16 * (size_t)q[t];
+        double p0[2], e1[2], e2[2];
+        for (int j = 0; j < 2; ++j) {
+            p0[j] = r[6 + ax[j]]; e1[j] = r[9 + ax[j]]; e2[j] = r[12 + ax[j]];
+            if (!in_range(p0[j]) || !in_range(e1[j]) || !in_range(e2[j])) return false;
+            const double s1 = p0[j] + e1[j], s2 = p0[j] + e2[j];
+            if (s1 - p0[j] != e1[j] || s1 - e1[j] != p0[j] || s2 - p0[j] != e2[j] || s2 - e2[j] != p0[j]) return false;
+            V[t][0][j] = p0[j]; V[t][1][j] = s1; V[t][2][j] = s2;
+        }
+        const double t1 = e1[0] * e2[1], t2 = e1[1] * e2[0], N = t1 - t2;
+        if (N == 0.0 || !((std::fabs(t1) + std::fabs(t2)) <= rt::kQuadKappa * std::fabs(N))) return false;
+        // u = ((P - p0) x e2) / N, v = (e1 x (P - p0)) / N in the plane
+        Coord& u = L[t][0]; Coord& v = L[t][1]; Coord& w = L[t][2];
+        u.g[0] = e2[1] / N; u.g[1] = -e2[0] / N; u.c = -(p0[0] * e2[1] - p0[1] * e2[0]) / N;
+        v.g[0] = -e1[1] / N; v.g[1] = e1[0] / N; v.c = -(e1[0] * p0[1] - e1[1] * p0[0]) / N;
+        w.g[0] = -u.g[0] - v.g[0]; w.g[1] = -u.g[1] - v.g[1]; w.c = 1.0 - u.c - v.c;
+        double mx[2] = {0.0, 0.0};
+        for (int k = 0; k < 2; ++k)
+            for (int c = 0; c < 4; ++c)
+                mx[k] = std::max(mx[k], std::fabs(L[t][k].g[0] * corner[c][0] + L[t][k].g[1] * corner[c][1] + L[t][k].c));
+        const double Qu = (W[0] * std::fabs(e2[1]) + W[1] * std::fabs(e2[0])) / std::fabs(N);
+        const double Qv = (W[0] * std::fabs(e1[1]) + W[1] * std::fabs(e1[0])) / std::fabs(N);
+        u.err = eps * (24.0 * mx[0] + 16.0 * Qu);
+        v.err = eps * (24.0 * mx[1] + 16.0 * Qv);
+        w.err = u.err + v.err + eps * (mx[0] + mx[1]);
+    }
+    auto at = [](const Coord& l, const double* P) { return l.g[0] * P[0] + l.g[1] * P[1] + l.c; };
+    for (int k1 = 0; k1 < 3; ++k1) {
+        const Coord& l1 = L[0][k1];
+        double mu = 0.0;
+        bool ok = true;
+        for (int j = 0; j < 3; ++j) {
+            const double x = at(l1, V[1][j]);
+            ok = ok && x <= rt::kQuadSlack;
+            mu = std::max(mu, -x);
+        }
+        if (!ok || !(mu > 0.0)) continue;
+        const double r1 = std::max(1.0, 1.0 / mu), r2 = std::max(1.0, mu);
+        if (!(r1 <= rt::kQuadRatio && r2 <= rt::kQuadRatio)) continue;
+        QuadLine ln;
+        ln.A[ax[0]] = (float)(r1 * l1.g[0]);
+        ln.A[ax[1]] = (float)(r1 * l1.g[1]);
+        ln.gamma = (float)(r1 * l1.c);
+        ln.side = 1;
+        for (int k = 0; k < 3; ++k) {
+            if (ln.A[k] == 0.0f) continue;
+            if (ln.A[k] < 0.0f) {
+                for (int m = 0; m < 3; ++m) ln.A[m] = -ln.A[m];
+                ln.gamma = -ln.gamma;
+                ln.side = 0;
+            }
+            break;
+        }
+        const double s = ln.side ? 1.0 : -1.0, A0 = ln.A[ax[0]], A1 = ln.A[ax[1]], G = ln.gamma;
+        auto sigma = [&](const double* P) { return A0 * P[0] + A1 * P[1] + G; };
+        for (int c = 0; c < 4; ++c) ok = ok && std::fabs(at(l1, corner[c]) - s * sigma(corner[c]) / r1) <= rt::kQuadSlack;
+        if (!ok) continue;
+        for (int k2 = 0; k2 < 3; ++k2) {
+            const Coord& l2 = L[1][k2];
+            bool ok2 = true;
+            for (int c = 0; c < 4; ++c) ok2 = ok2 && std::fabs(at(l2, corner[c]) + s * sigma(corner[c]) / r2) <= rt::kQuadSlack;
+            if (!ok2) continue;
+            // quad_bound: the classifier's error on sigma~, then each dropped record's
+            const double Ms = std::fabs(A0) * Cm[0] + std::fabs(A1) * Cm[1] + std::fabs(G);
+            const double Ecls = eps * (std::fabs(A0) * (4.0 * W[0] + Cm[0]) + std::fabs(A1) * (4.0 * W[1] + Cm[1]) + 3.0 * Ms);
+            const double E = std::max(Ecls + r1 * (rt::kQuadSlack + l1.err), Ecls + r2 * (rt::kQuadSlack + l2.err));
+            if (!((double)rt::kQuadBand >= rt::kQuadSafety * E)) return false;
+            out = ln;
+            return true;
+        }
+    }
+    return false;
+}
+
 // The shell of a clustered scene (HostScene::brute_shell; option "brute_shell", mode 0 off, < 0 auto, > 0 force):
 // a box S with lo < hi, finite, on every axis, and the single slots that are faces of it -- a slot is a face when
 // its box is flat on one axis at S's lower or upper bound there and equals S's range on the other two, every
@@ -553,12 +664,13 @@ bool near_safe(const HostScene& hs, const float* b) {
 // one is a third coplanar record: it stays a single).  auto: only from kShellMinFaces faces; force: from the two
 // that define a shell.  brute_cbox, brute_crow and nsingle are untouched; the singles that are no face are copied
 // behind the record in their order.
-void build_shell(HostScene& hs, int mode) {
+void build_shell(HostScene& hs, int mode, int quad) {
     hs.brute_shell.clear();
     hs.nshell = 0;
     hs.nrest = 0;
     hs.shell_floor = 0.0f;
     hs.shell_mask = 0;
+    hs.nquad = 0;
     if (mode == 0 || hs.ncluster == 0) return;
     const int32_t n = hs.nsingle;
     auto bits = [](float f) {
@@ -647,6 +759,31 @@ void build_shell(HostScene& hs, int mode) {
         r[8 + 2 * f] = face[f] < 0 ? as_f32(-1) : box(face[f])[6];
         r[9 + 2 * f] = face[f] < 0 ? as_f32(-1) : box(face[f])[7];
     }
+    // the rows (rt_layout.h kShellRows): each face's packed records, and its line where it is split
+    float S6[6];
+    for (int k = 0; k < 6; ++k) std::memcpy(S6 + k, &(*best)[k], 4);
+    for (int f = 0; f < rt::kShellRows; ++f) {
+        float* row = r + 4 * rt::kShellRowF4 + 8 * f;
+        uint32_t both = ~0u, pos = ~0u, neg = ~0u, flags = 0;
+        if (f < 6 && face[f] >= 0) {
+            const uint32_t q0 = (uint32_t)as_i32(box(face[f])[6]), q1 = (uint32_t)as_i32(box(face[f])[7]);
+            // records are queued as 16-bit ranks (the ring's entries): brute_max is far below 0xffff
+            both = pos = neg = (q0 & 0xffffu) | (q1 << 16);
+            QuadLine ln;
+            if (quad != 0 && q1 < 0xffffu && quad_split(hs, box(face[f]), S6, ln)) {
+                for (int k = 0; k < 3; ++k) row[k] = ln.A[k];
+                row[3] = ln.gamma;
+                pos = (ln.side ? q0 : q1) | 0xffff0000u;
+                neg = (ln.side ? q1 : q0) | 0xffff0000u;
+                flags = 1u | (ln.side ? 2u : 0u);
+                ++hs.nquad;
+            }
+        }
+        row[4] = as_f32((int32_t)both); row[5] = as_f32((int32_t)pos);
+        row[6] = as_f32((int32_t)neg); row[7] = as_f32((int32_t)flags);
+    }
+    // the number of split faces above the face count: the kernels read it as the rule's enable
+    r[7] = as_f32((int32_t)best_slots.size() | (hs.nquad << 8));
     float* o = r + rt::kShellRecF;
     for (size_t s = 0; s < nr4; ++s) pad_box(o + 8 * s);
     for (int32_t s = 0; s < n; ++s)
@@ -672,7 +809,7 @@ void build_shell(HostScene& hs, int mode) {
 // RT_BVH_REFERENCE keeps the reference's tree, RT_BVH_SAH regroups its leaf
 // boxes (bvh_sah.cpp); both give the same hits.
 bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int layout, int brute_max, int cluster,
-               int shell, std::string& why) {
+               int shell, int quad, std::string& why) {
     if (nn <= 0) {
         why = "empty BVH";
         return false;
@@ -757,6 +894,7 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
     hs.brute_near.clear();
     hs.shell_floor = 0.0f;
     hs.shell_mask = 0;
+    hs.nquad = 0;
     if ((int64_t)leaves.size() <= (int64_t)brute_max) {
         std::vector<int32_t> by_rank(leaves.size());
         for (int32_t n : leaves) by_rank[rank[T[n]]] = n;
@@ -812,7 +950,7 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
         hs.brute_near.assign((size_t)hs.nbox, 0);
         for (int32_t g = 0; g < hs.nbox; ++g) hs.brute_near[g] = near_safe(hs, hs.brute_box.data() + 8 * (size_t)g);
         build_clusters(hs, cluster);
-        build_shell(hs, shell);
+        build_shell(hs, shell, quad);
     }
     if (layout == RT_BVH_SAH && leaves.size() > 1) {
         std::vector<float> lb(6 * leaves.size());
@@ -839,8 +977,8 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
 namespace rt {
 
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
-                  int shell, std::string& why) {
-    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, shell, why) : true;
+                  int shell, int quad, std::string& why) {
+    hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, shell, quad, why) : true;
     if (hs.fast_ok && ntri > 0) {
         // the FAST kernels' Moller-Trumbore reciprocal (rt_device.h mt_recip) is IEEE-exact for
         // |a| <= 2^126, a = e1 . (d x e2) with |d| = 1: bound |e1| |e2| (finite edges; an infinite or
@@ -865,7 +1003,7 @@ void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, in
     }
     if (!hs.fast_ok) { hs.brute.clear(); hs.brute_box.clear(); hs.nbrute = 0; hs.nbox = 0; }
     if (hs.nbrute == 0) { hs.brute_cbox.clear(); hs.brute_crow.clear(); hs.ncluster = 0; hs.nsingle = 0; hs.brute_near.clear(); }
-    if (hs.ncluster == 0) { hs.brute_shell.clear(); hs.nshell = 0; hs.nrest = 0; hs.shell_floor = 0.0f; hs.shell_mask = 0; }
+    if (hs.ncluster == 0) { hs.brute_shell.clear(); hs.nshell = 0; hs.nrest = 0; hs.shell_floor = 0.0f; hs.shell_mask = 0; hs.nquad = 0; }
     if (!hs.fast_ok || hs.wdepth > 64) { hs.wnodes.clear(); hs.wleaves.clear(); hs.nwnodes = 0; hs.wdepth = 1; }
     // render kernels keep kStackLds entries in LDS and spill deeper ones to HBM; the single-ray
     // debug kernel keeps the whole stack in LDS (int2 entries, 128 lanes): depth <= 64
@@ -885,7 +1023,7 @@ namespace {
 
 int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                    int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                   int brute_max, int cluster, int shell, std::string& msg, std::string& why) {
+                   int brute_max, int cluster, int shell, int quad, std::string& msg, std::string& why) {
     if (nvp < 0 || nvp % 3 || nvn < 0 || nvn % 3 || nface < 0 || nface % 10 || nmat <= 0 || nmat % 6 || nbvh < 0 ||
         nbvh % 9)
         return fail(msg, RT_ERR_ARG,
@@ -962,7 +1100,7 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
             }
         }
     }
-    pack_checked(hs, bvh9, NB, T, layout, brute_max, cluster, shell, why);
+    pack_checked(hs, bvh9, NB, T, layout, brute_max, cluster, shell, quad, why);
     return RT_OK;
 }
 
@@ -971,10 +1109,10 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
 // No C++ exception leaves the C ABI: a scene too large for host memory is an error status.
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, int cluster, int shell, std::string& msg, std::string& why) {
+                  int brute_max, int cluster, int shell, int quad, std::string& msg, std::string& why) {
     try {
         return scene_prepare_(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout, brute_max, cluster, shell,
-                              msg, why);
+                              quad, msg, why);
     } catch (const std::bad_alloc&) {
         hs = HostScene();
         return fail(msg, RT_ERR_ARG, "scene too large for host memory");
@@ -1000,7 +1138,7 @@ extern "C" int rt_scene_check(const float* vp, int64_t nvp, const float* vn, int
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, -1, -1, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, -1, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc == RT_OK && info) {
         info[0] = hs.ntri;
@@ -1031,7 +1169,7 @@ extern "C" int rt_debug_brute_layout(const float* vp, int64_t nvp, const float* 
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, -1, -1, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, -1, -1, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.nbox;
@@ -1061,7 +1199,7 @@ extern "C" int rt_debug_brute_clusters(const float* vp, int64_t nvp, const float
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, cluster, -1, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, cluster, -1, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.ncluster;
@@ -1092,7 +1230,7 @@ extern "C" int rt_debug_brute_shell(const float* vp, int64_t nvp, const float* v
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = hs.nshell;
@@ -1122,7 +1260,7 @@ extern "C" int rt_debug_brute_near(const float* vp, int64_t nvp, const float* vn
         return RT_ERR_ARG;
     }
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
-                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, msg, why);
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, -1, msg, why);
     g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
     if (rc != RT_OK) return rc;
     info[0] = (int64_t)hs.brute_near.size();
@@ -1130,5 +1268,55 @@ extern "C" int rt_debug_brute_near(const float* vp, int64_t nvp, const float* vn
     *floor = hs.shell_floor;
     const int64_t n = std::min<int64_t>(cap, info[0]);
     for (int64_t g = 0; g < n; ++g) flags[g] = hs.brute_near[(size_t)g];
+    return RT_OK;
+}
+
+extern "C" int rt_debug_brute_quad(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                   int layout, int cluster, int shell, int quad, int32_t flags[6], float lines[24],
+                                   int32_t words[18], float recs[108], float guard[3], int64_t info[2]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (cluster < -1 || cluster > 1 || shell < -1 || shell > 1) {
+        g_check_error = "brute_cluster and brute_shell must be -1 (auto), 0 (off) or 1 (force)";
+        return RT_ERR_ARG;
+    }
+    if (quad < -1 || quad > 1) {
+        g_check_error = "brute_quad must be -1 (auto), 0 (off) or 1 (auto)";
+        return RT_ERR_ARG;
+    }
+    if (!info || !flags || !lines || !words || !recs || !guard) {
+        g_check_error = "null info, flags, lines, words, recs or guard";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, quad, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[0] = hs.nshell;
+    info[1] = hs.nquad;
+    guard[0] = rt::kQuadBand; guard[1] = rt::kQuadGraze; guard[2] = rt::kQuadDirMax;
+    for (int f = 0; f < 6; ++f) {
+        flags[f] = 0;
+        for (int k = 0; k < 4; ++k) lines[4 * f + k] = 0.0f;
+        for (int k = 0; k < 3; ++k) words[3 * f + k] = -1;
+        for (int k = 0; k < 18; ++k) recs[18 * f + k] = 0.0f;
+        if (hs.nshell == 0) continue;
+        const float* row = hs.brute_shell.data() + 4 * rt::kShellRowF4 + 8 * f;
+        std::memcpy(lines + 4 * f, row, 16);
+        std::memcpy(words + 3 * f, row + 4, 12);
+        std::memcpy(flags + f, row + 7, 4);
+        // the records as Moller-Trumbore reads them: p0, e1, e2 of the first, then of the second
+        const uint32_t both = (uint32_t)words[3 * f];
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t q = j ? both >> 16 : both & 0xffffu;
+            if (both != ~0u && q != 0xffffu && (int32_t)q < hs.nbrute)
+                std::memcpy(recs + 18 * f + 9 * j, hs.brute.data() + 16 * (size_t)q + 6, 9 * sizeof(float));
+        }
+    }
     return RT_OK;
 }

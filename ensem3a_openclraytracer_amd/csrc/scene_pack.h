@@ -32,11 +32,14 @@ struct HostScene {
     std::vector<float> brute_crow; // 8 floats per cluster: union lo.x hi.x lo.y hi.y lo.z hi.z | first slot, box count
     int32_t ncluster = 0, nsingle = 0;   // clusters; single (real) slots at the head of brute_cbox
     // the shell among the single slots (scene_pack.cpp build_shell, option "brute_shell"; nshell = 0: none):
-    // kShellRecF floats -- the shell box lo.x hi.x lo.y hi.y | lo.z hi.z, nrest, nshell (int bits) | the two
+    // kShellRecF floats -- the shell box lo.x hi.x lo.y hi.y | lo.z hi.z, nrest, nshell | nquad << 8 (int bits) | the two
     // records of the faces -x +x | -y +y | -z +z (int bits; an absent face -1 -1) -- then the nrest singles that
     // are no face, 8 floats per slot in brute_cbox order, padded to whole groups
+    // -- | kShellRows rows of 8 floats (rt_layout.h: each face's line, packed records and flags, option
+    // "brute_quad"; scene_pack.cpp quad_split)
     std::vector<float> brute_shell;
     int32_t nshell = 0, nrest = 0;       // faces of the shell; single slots outside it
+    int32_t nquad = 0;                   // faces the packer split (option "brute_quad")
     // option "brute_near" (scene_pack.cpp near_safe): 1 for each of the nbox boxes of brute_box that
     // is near-safe -- a ray that passes it closer than rt::kNearFloor cannot hit its records -- and the floor of the
     // shell's face tests: rt::kNearFloor when the shell's every face is such a box, else 0
@@ -56,11 +59,12 @@ struct HostScene {
 // reason when the FAST layouts are unavailable (hs.fast_ok false; the REF traversal then serves).
 int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
                   int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh, int layout,
-                  int brute_max, int cluster, int shell, std::string& msg, std::string& why);
+                  int brute_max, int cluster, int shell, int quad, std::string& msg, std::string& why);
 
 // pack_fast + the limits of the FAST kernels; sets hs.fast_ok (an option change repacks with it).
-// cluster, shell: options "brute_cluster", "brute_shell" (0 off, -1 auto, 1 force; include/rt_debug.h).
+// cluster, shell: options "brute_cluster", "brute_shell" (0 off, -1 auto, 1 force; include/rt_debug.h); quad: option
+// "brute_quad" (0: no face of the shell is split, else auto).
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
-                  int shell, std::string& why);
+                  int shell, int quad, std::string& why);
 
 }  // namespace rt

@@ -21,6 +21,10 @@
  *                  hit condition's 1e-4) as their lower clamp instead of 0 where the packer found every face
  *                  near-safe, so a ray is not tested against the triangles of the wall it starts on (0 off: clamp
  *                  0, -1 auto; 1 means auto: there is no way to force an unsafe floor)
+ *   "brute_quad"   clustered brute force with a shell: a ray that is sure which side of a wall's diagonal it leaves
+ *                  through queues that side's triangle alone (kQuadBand, kQuadGraze in rt_layout.h; the packer
+ *                  splits a wall only where its error bound allows it); packs the scene again (0 off, -1 auto; 1
+ *                  means auto: an unsafe wall cannot be forced)
  *   "brute_refill" brute force, one lane per pixel: a wave hands out jobs once this many lanes are free, 2..64
  *                  (0 or 1 every free lane at once, -1 auto: 4 on tiles of >= 1.5 pixels per resident lane)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
@@ -152,9 +156,9 @@ int rt_debug_brute_clusters(const float* V_p, int64_t n_vp, const float* V_n, in
  * on the other two, every equality bitwise.  The kernels of the clustered loop test the faces from S's six plane
  * distances, computed once per ray, and the other singles from a slot array of their own.  info[0] = faces (0: no
  * shell, the array is empty; auto takes a shell from 3 faces, force from the 2 that define one), info[1] = single slots that are no face,
- * info[2] = floats in the array: 20 for the record -- S as lo.x hi.x lo.y hi.y lo.z hi.z, the int bits of info[1]
- * and info[0], then the int bits of the two records of the faces -x, +x, -y, +y, -z, +z (-1 -1: no such face) --
- * then 8 per remaining single, in their order, padded to a whole group of 4 as above. */
+ * info[2] = floats in the array: 76 for the record -- S as lo.x hi.x lo.y hi.y lo.z hi.z, the int bits of info[1]
+ * and of info[0] | split faces << 8 (rt_debug_brute_quad), then the int bits of the two records of the faces -x, +x, -y, +y, -z, +z (-1 -1: no such face),
+ * then seven rows of 8 (rt_debug_brute_quad; the six faces and "no face") -- then 8 per remaining single, in their order, padded to a whole group of 4 as above. */
 int rt_debug_brute_shell(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
                          int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
                          int layout, int cluster, int shell, float* rec, int64_t cap, int64_t info[3]);
@@ -167,6 +171,19 @@ int rt_debug_brute_shell(const float* V_p, int64_t n_vp, const float* V_n, int64
 int rt_debug_brute_near(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
                         int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
                         int layout, int cluster, int shell, int32_t* flags, int64_t cap, float* floor, int64_t info[2]);
+
+/* Host-only (no device): the walls option "brute_quad" = quad (-1 auto, 0 off, 1 auto) splits in the shell of
+ * rt_debug_brute_shell(cluster, shell), per face position -x +x -y +y -z +z.  flags[f]: bit 0 the face is split,
+ * bit 1 its first record lies on the side sigma >= 0 of its line; lines[4 f ..]: A.x A.y A.z gamma of sigma(P) =
+ * A . P + gamma (A zero on the face's axis, its first non-zero component positive; all zero when not split);
+ * words[3 f ..]: the face's packed records first | second << 16 -- both, the one queued for sigma >= 0, the one for
+ * sigma < 0 (-1: no such face; 0xffff for a missing second record); recs[18 f ..]: the face's first and second
+ * record as Moller-Trumbore reads them, p0 e1 e2 each (zeros where absent); guard = kQuadBand, kQuadGraze, kQuadDirMax
+ * (rt_layout.h); info[0] = faces of the shell, info[1] = split faces. */
+int rt_debug_brute_quad(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                        int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                        int layout, int cluster, int shell, int quad, int32_t flags[6], float lines[24],
+                        int32_t words[18], float recs[108], float guard[3], int64_t info[2]);
 
 /* No device call: the rule for sample slices on a brute-force scene (option "slices" = option: -1 auto, 0 off,
  * K) for a launch over a tile of nloc pixels on a device that keeps `lanes` lanes of the kernel resident, which
@@ -187,8 +204,9 @@ int rt_debug_last_slices(void);
  * team size, the walk's team size, the slice word (rt_debug_last_slices) and R (rt_debug_last_refill) of its
  * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block; out[17] = 1 when the kernel
  * walked a shell (option "brute_shell": the clustered loop on a scene that has one), else 0; out[18] = 1 when it
- * walked that shell with a non-zero floor (option "brute_near"), else 0. */
-int rt_debug_last_launch(int32_t out[19]);
+ * walked that shell with a non-zero floor (option "brute_near"), else 0; out[19] = 1 when that shell's record has
+ * split walls (option "brute_quad"), else 0. */
+int rt_debug_last_launch(int32_t out[20]);
 
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
