@@ -435,7 +435,37 @@ constexpr unsigned BRUTE_RING = 256u;
 constexpr unsigned BRUTE_OWNERS = 128u;   // owner list of the clustered loop (entries; a power of two)
 constexpr int BRUTE_INV_OFF = 64 * 6 * 4 + 64 * 8 + (BRUTE_RING + 64) * 4;
 // ray table | best keys | pair ring + dummy slots | clustered loop: inverse directions [3][64] | owner list
-constexpr int BRUTE_WAVE_LDS = BRUTE_INV_OFF + 64 * 3 * 4 + BRUTE_OWNERS * 4;
+// Build define RT_CHAIN_STAMPS=1 (tools/variants.py; never the product build): the clustered one-lane product kernel
+// reads the wave clock at the borders of seven sections of its loop -- kStamp* -- and adds the differences to the
+// counts buffer (tools/chain_stamps.py).  One lane keeps the sums and the last clock in 64 bytes behind its wave's
+// area: 7 sums | the last clock
+#ifndef RT_CHAIN_STAMPS
+#define RT_CHAIN_STAMPS 0
+#endif
+#ifndef RT_SHADE_ROWS
+#define RT_SHADE_ROWS 1   // the one-lane brute-force kernels' shading rows (render_kernel ROWS); 0: an A/B build
+#endif
+constexpr int BRUTE_STAMP_OFF = BRUTE_INV_OFF + 64 * 3 * 4 + BRUTE_OWNERS * 4;
+constexpr int BRUTE_WAVE_LDS = BRUTE_STAMP_OFF + (RT_CHAIN_STAMPS ? 64 : 0);
+// loop head -> trace entry | entry -> after the shell step | the non-face singles | the cluster loop with its item
+// batches | all MT batches, wherever they run | the tail batches and the epilogue | trace exit -> loop head (an
+// iteration that traces nothing falls here whole)
+enum { kStampHead = 0, kStampShell, kStampSingles, kStampClusters, kStampBatches, kStampTail, kStampRest, kStampN };
+// Only trace_brute_compact<COUNT = false, CLU = true> stamps -- the clustered product instantiations of render_kernel,
+// each of which zeroes the sums first and flushes them last (its STAMPS); the query, team, lock-step and instrumented
+// traces have CLU false or COUNT true and compile no stamp.
+// The section `done` ends here: the wave's first active lane adds the clock's advance since the last stamp to it
+__device__ __forceinline__ void chain_stamp(char* wl, int done) {
+#if RT_CHAIN_STAMPS
+    const unsigned long long act = __ballot(1);
+    if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)act) - 1u) {
+        unsigned long long* st = reinterpret_cast<unsigned long long*>(wl + BRUTE_STAMP_OFF);
+        const unsigned long long now = clock64();
+        st[done] += now - st[kStampN];
+        st[kStampN] = now;
+    }
+#endif
+}
 // at most 64 owners join fewer than 64 / kClusterSlots + 2 waiting ones; an owner entry keeps its first slot above bit 8
 static_assert(kClusterLockNum >= 0 && kClusterLockNum <= 8 && BRUTE_OWNERS >= 64 + 64 / kClusterSlots + 2, "owner list");
 
@@ -534,7 +564,9 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
     const float ix = dev_recip(d.x), iy = dev_recip(d.y), iz = dev_recip(d.z);
     float bk = 1000.0f;
     unsigned head = 0, tail = 0;   // wave-uniform ring positions
+    [[maybe_unused]] int sec = kStampShell;   // (RT_CHAIN_STAMPS: the section the wave is in)
     auto run_batch = [&](int n) __attribute__((always_inline)) {
+        if constexpr (CLU && !COUNT) chain_stamp(wl, sec);
         if (myrank < n) {
             const unsigned e = ring[(head + myrank) & (BRUTE_RING - 1)];
             const unsigned ow = e >> 16, q = e & 0xffffu;
@@ -559,6 +591,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         }
         head += n;
         wave_lds_sync();
+        if constexpr (CLU && !COUNT) chain_stamp(wl, kStampBatches);
     };
     // queue the passing (owner, triangle) pairs of records qa and qb (qb wave-uniform; < 0: none),
     // which share one leaf box; run batches while a full wave of pairs is queued.  The ring holds
@@ -756,7 +789,9 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             sb = ConstF4{sh.p + kShellRecF};
             ns = __float_as_int(h1.z);
         }
+        if constexpr (!COUNT) { chain_stamp(wl, kStampShell); sec = kStampSingles; }
         lockstep(sb, 0, ns);
+        if constexpr (!COUNT) { chain_stamp(wl, kStampSingles); sec = kStampClusters; }
         unsigned ihead = 0, itail = 0;   // wave-uniform item positions; itail is a multiple of kClusterSlots
         // one batch of n <= nact items: fewer than nact pairs are queued before it and it adds at most 2 n
         auto run_items = [&](int n) __attribute__((always_inline)) {
@@ -814,6 +849,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             while ((int)(itail - ihead) >= nact) run_items(nact);
         }
         while (itail != ihead) run_items(min((int)(itail - ihead), nact));
+        if constexpr (!COUNT) { chain_stamp(wl, kStampClusters); sec = kStampTail; }
     } else if (ts == 1) {
         if constexpr (COUNT) {
             // the instrumented loop counts the pairs the clustered product kernel queues (option "brute_quad"): the
@@ -881,6 +917,7 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
         // triangle index: the record's last float4 (read from the LDS copy when it is staged)
         best.tri = __float_as_int(mtrec[mtstride * (unsigned)(key & 0xffffffffu) + 2].w);
     }
+    if constexpr (CLU && !COUNT) chain_stamp(wl, kStampTail);
     return best;
 }
 
@@ -943,11 +980,15 @@ inline size_t stack_lds_bytes(const DevScene& sc, int traversal, int block) {
     const size_t lds = (size_t)depth * block * sizeof(int);
     return traversal == TRAV_FAST && sc.nbrute > 0 ? std::max(lds, (size_t)(block / 64) * BRUTE_WAVE_LDS) : lds;
 }
-// ... of the brute-force kernels (BRUTE_ != 0), which stage the scene: records, boxes, shading, materials, clusters
-inline size_t brute_lds_bytes(const DevScene& sc, int block) {
-    return (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.nbox * 32 +
-           (size_t)sc.ntri * 64 + (size_t)sc.nmat * (4 * kMatF) + (size_t)sc.ncslot * 32 +
-           (sc.shell ? (size_t)kShellRows * 32 : 0);
+// ... of the brute-force kernels (BRUTE_ != 0), which stage the scene (render_kernel's prologue has the layout).
+// team: the team kernel, with the distinct leaf boxes, tri_shade's copy and the material table; the one-lane
+// kernels stage a shading row of 32 bytes per triangle in place of the last two, and no boxes
+inline size_t brute_lds_bytes(const DevScene& sc, int block, bool team) {
+    if (!RT_SHADE_ROWS) team = true;   // (an A/B build without the rows: every kernel is priced as the parent priced it)
+    const size_t shade = team ? (size_t)sc.nbox * 32 + (size_t)sc.ntri * 16 + (size_t)sc.nmat * (4 * kMatF)
+                              : (size_t)sc.ntri * 32;
+    return (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + shade + (size_t)sc.ntri * 48 +
+           (size_t)sc.ncslot * 32 + (sc.shell ? (size_t)kShellRows * 32 : 0);
 }
 // ... and what the SMEM walks stage behind their stack: the BVH2 nodes and the triangles
 inline size_t staged_scene_bytes(const DevScene& sc) {
@@ -1144,6 +1185,15 @@ struct Mat {
     rtm_f3 color;
     float rough;
 };
+
+// a material from a triangle's staged row (render_kernel ROWS): n.xyz type | colour.xyz rough
+__device__ __forceinline__ Mat row_mat(float4 r0, float4 r1) {
+    Mat r;
+    r.type = (int)r0.w;
+    r.color = rtm_v3(r1.x, r1.y, r1.z);
+    r.rough = r1.w;
+    return r;
+}
 
 // Device material rows are padded to kMatF = 8 floats (rt_internal.h DevScene::mat): two vector loads.
 __device__ __forceinline__ Mat load_mat(const float* __restrict__ m, int idx) {

@@ -92,22 +92,41 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     const float4* tshade = S.tri_shade;
     const float4* tframe = S.tri_frame;
     const float* tmat = S.mat;
+    // ROWS (the one-lane brute-force kernels): in place of tri_shade's copy and the material table's, one row of two
+    // float4 per triangle, n.xyz type | colour.xyz rough -- copies of the words tri_shade and the triangle's material
+    // hold, so a shading look-up is one read and not a read of the material's index with a dependent read of the
+    // table.  The layout, which brute_lds_bytes (rt_device.h) prices: records | the team kernel's boxes | rows, or
+    // tri_shade and behind the frames the materials | frames | the clustered loop's slots and the shell's rows
+    constexpr bool ROWS = RT_SHADE_ROWS && (BRUTE == 1 || BRUTE == 3);   // (RT_SHADE_ROWS=0: an A/B build without them)
+    const float4* trow = nullptr;
     if (BRUTE) {
         float4* lr = reinterpret_cast<float4*>(reinterpret_cast<char*>(lds_stack) + (B / 64) * BRUTE_WAVE_LDS);
-        float4* lb = lr + 3 * S.nbrute;                  // the distinct leaf boxes (team box tests)
-        if (BRUTE == 2) {
-            for (int q = threadIdx.x; q < 2 * S.nbox; q += B) lb[q] = S.brute_box[q];
-            boxrec = lb;
+        float4* ls = lr + 3 * S.nbrute;
+        if (BRUTE == 2) {   // the distinct leaf boxes (team box tests)
+            for (int q = threadIdx.x; q < 2 * S.nbox; q += B) ls[q] = S.brute_box[q];
+            boxrec = ls;
+            ls += 2 * S.nbox;
         }
-        float4* ls = lb + 2 * S.nbox;
-        float4* lf = ls + S.ntri;
+        float4* lf = ls + (ROWS ? 2 : 1) * S.ntri;
         float* lm = reinterpret_cast<float*>(lf + 3 * S.ntri);
         for (int q = threadIdx.x; q < 3 * S.nbrute; q += B) lr[q] = S.brute[4 * (q / 3) + 1 + q % 3];
-        for (int q = threadIdx.x; q < S.ntri; q += B) ls[q] = S.tri_shade[q];
         for (int q = threadIdx.x; q < 3 * S.ntri; q += B) lf[q] = S.tri_frame[q];
-        for (int q = threadIdx.x; q < kMatF * S.nmat; q += B) lm[q] = S.mat[q];
+        if constexpr (ROWS) {
+            for (int q = threadIdx.x; q < S.ntri; q += B) {
+                const float4 sh = S.tri_shade[q];
+                const float* m = S.mat + kMatF * __float_as_int(sh.w);
+                ls[2 * q] = make_float4(sh.x, sh.y, sh.z, m[0]);
+                ls[2 * q + 1] = make_float4(m[1], m[2], m[3], m[4]);
+            }
+            trow = ls;
+        } else {
+            for (int q = threadIdx.x; q < S.ntri; q += B) ls[q] = S.tri_shade[q];
+            for (int q = threadIdx.x; q < kMatF * S.nmat; q += B) lm[q] = S.mat[q];
+            tshade = ls;
+            tmat = lm;
+        }
         if (BRUTE == 3) {   // the clustered loop's item tests read their slots here
-            float4* lc = reinterpret_cast<float4*>(lm + kMatF * S.nmat);
+            float4* lc = reinterpret_cast<float4*>(lm + (ROWS ? 0 : kMatF * S.nmat));   // (behind the table, where it is staged)
             for (int q = threadIdx.x; q < 2 * S.ncslot; q += B) lc[q] = S.brute_cbox[q];
             // ... and the shell's rows behind them (rt_layout.h kShellRows; trace_brute_compact's one queue step
             // reads a lane's face's row), at boxrec + S.shell
@@ -117,9 +136,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         }
         __syncthreads();
         mtrec = lr;
-        tshade = ls;
         tframe = lf;
-        tmat = lm;
+    }
+    // (RT_CHAIN_STAMPS, rt_device.h: the clustered product kernel's section clocks, in its wave's LDS area)
+    // -- every instantiation whose trace stamps (trace_brute_compact<COUNT, CLU>: CLU && !COUNT) zeroes and flushes them
+    constexpr bool STAMPS = RT_CHAIN_STAMPS && BRUTE == 3 && !COUNT;
+    [[maybe_unused]] char* const stamp_wl = reinterpret_cast<char*>(lds_stack) + (threadIdx.x >> 6) * BRUTE_WAVE_LDS;
+    if constexpr (STAMPS) {
+        if ((threadIdx.x & 63) == 0) {
+            unsigned long long* st = reinterpret_cast<unsigned long long*>(stamp_wl + BRUTE_STAMP_OFF);
+            for (int q = 0; q < kStampN; ++q) st[q] = 0;
+            st[kStampN] = clock64();
+        }
     }
     const LaunchConst& C = *lconst;   // uniform: scalar loads, no VGPRs
     // SMEM: the whole BVH2 node array and triangle array of a small scene are
@@ -213,6 +241,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     };
 
     while (true) {
+        if constexpr (STAMPS) chain_stamp(stamp_wl, kStampRest);
         // instrumented build: wave cycles in the trace (cyc_trav) and in the rest of the loop (cyc_shade:
         // every iteration's time, the trace's subtracted below; unsigned wrap-around cancels)
         if (COUNT && lane == 0) {
@@ -345,9 +374,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             } else if (tri < 0) {
                 so = rtm_scale(rtm_mul(so, sample_ibl_if<COUNT>(S, C, Rd, e4, c)), e4);
             } else {
-                const float4 sh = tshade[tri];
+                const float4 sh = ROWS ? trow[2 * tri] : tshade[tri];
                 const rtm_f3 n = xyz(sh);
-                const Mat cm = load_mat(tmat, __float_as_int(sh.w));
+                const Mat cm = ROWS ? row_mat(sh, trow[2 * tri + 1]) : load_mat(tmat, __float_as_int(sh.w));
                 if (cm.type == 0) {
                     so = rtm_scale(so, cm.rough);
                 } else {
@@ -415,6 +444,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         const rtm_f3 to = (phase == PRIMARY) ? C.position : Bo;
         const rtm_f3 td = (phase == PRIMARY) ? cd : ((phase == BOUNCE) ? Bd : C.sun);
         const unsigned long long t_tr = COUNT ? clock64() : 0;
+        if constexpr (STAMPS) chain_stamp(stamp_wl, kStampHead);
         const Hit h = trace<TRAV, COUNT, SMEM, OVF, BRUTE != 0, BRUTE == 3>(S, nodes, tris, to, td, stk, B, lst, c, mtrec, ts, boxrec);
         if (COUNT && lane == __ffsll((long long)__ballot(1)) - 1) {   // the first tracing lane, once per wave
             const unsigned long long dt = clock64() - t_tr;
@@ -436,7 +466,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             continue;
         }
         if (LOG && logme) {
-            const int hm = h.tri >= 0 ? __float_as_int(tshade[h.tri].w) : 0;
+            const int hm = h.tri >= 0 ? __float_as_int(S.tri_shade[h.tri].w) : 0;   // (the global table: the rows hold no index)
             log_event(F, phase == BOUNCE ? 1.0f : 2.0f, j, Bo, td, h.tri >= 0 ? h.k : -1.0f, hm, so);
         }
         int sun_hit = -2;   // the shadow ray's hit for the sun term below (-1 = miss; -2 = no sun term now)
@@ -446,7 +476,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         if (phase == BOUNCE) {
             if (h.tri >= 0) {
                 tri = h.tri; k = h.k;
-                const Mat bm = load_mat(tmat, __float_as_int(tshade[h.tri].w));
+                const Mat bm = ROWS ? row_mat(trow[2 * h.tri], trow[2 * h.tri + 1])
+                                    : load_mat(tmat, __float_as_int(tshade[h.tri].w));
                 if (bm.type != 0) {
                     if (j == maxB) {
                         so = rtm_v3(0, 0, 0);
@@ -473,10 +504,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         if (sun_hit != -2) {  // SUN (Raytracing.cl:115-137)
             rtm_f3 sunLight = rtm_v3(0, 0, 0);
             if (COUNT) c.sun++;
-            const Mat cm = load_mat(tmat, __float_as_int(tshade[tri].w));
+            const Mat cm = ROWS ? row_mat(trow[2 * tri], trow[2 * tri + 1])
+                                : load_mat(tmat, __float_as_int(tshade[tri].w));
             if (sun_hit < 0 && cm.type != 3) sunLight = rtm_v3(e3, e3, e3);
             if (sun_hit >= 0) {
-                const Mat sm = load_mat(tmat, __float_as_int(tshade[sun_hit].w));
+                const Mat sm = ROWS ? row_mat(trow[2 * sun_hit], trow[2 * sun_hit + 1])
+                                    : load_mat(tmat, __float_as_int(tshade[sun_hit].w));
                 if (sm.type == 3) sunLight = rtm_scale(sm.color, e3);
             }
             const rtm_f3 envLight = rtm_scale(sample_ibl_if<COUNT>(S, C, Bd, e4, c), e4);
@@ -504,6 +537,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 so = rtm_v3(1, 1, 1);
                 phase = PREP;
             }
+        }
+    }
+    if constexpr (STAMPS) {
+        if ((threadIdx.x & 63) == 0 && counts) {
+            const unsigned long long* st = reinterpret_cast<const unsigned long long*>(stamp_wl + BRUTE_STAMP_OFF);
+            for (int q = 0; q < kStampN; ++q) atomicAdd(&counts[q], st[q]);
         }
     }
     if (COUNT) {
@@ -1289,12 +1328,36 @@ KernelKey choose_kernel(const DevScene& sc, const FrameParams& fp, int traversal
         return k;
     }
     // brute force stages the scene in LDS: only while two blocks still fit a CU
-    if (sc.ntri > 0 && sc.nbrute > 0 && brute_lds_bytes(sc, block) <= 80 * 1024) k.brute = 1;
+    if (sc.ntri > 0 && sc.nbrute > 0 && std::max(brute_lds_bytes(sc, block, true), brute_lds_bytes(sc, block, false)) <= 80 * 1024) k.brute = 1;
     else k.smem = stage_in_lds(sc);
     return k;
 }
 
 #endif  // !RT_ACCUM_TU
+
+#if RT_CHAIN_STAMPS
+namespace {
+// the stamps' sums (kStampN words), shared by every product launch of this translation unit
+unsigned long long* chain_stamp_buffer() {
+    static unsigned long long* p = [] {
+        unsigned long long* q = nullptr;
+        if (hipMalloc(&q, kStampN * sizeof(unsigned long long)) != hipSuccess) return (unsigned long long*)nullptr;
+        if (hipMemset(q, 0, kStampN * sizeof(unsigned long long)) != hipSuccess) return (unsigned long long*)nullptr;
+        return q;
+    }();
+    return p;
+}
+}  // namespace
+#ifndef RT_ACCUM_TU
+// tools/chain_stamps.py: the sums since the last call (the one-shot frames' launches), then zeroed; blocking
+extern "C" __attribute__((visibility("default"))) int rt_debug_chain_stamps(unsigned long long out[kStampN]) {
+    unsigned long long* p = chain_stamp_buffer();
+    if (!p || hipDeviceSynchronize() != hipSuccess) return 1;
+    if (hipMemcpy(out, p, kStampN * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+    return hipMemset(p, 0, kStampN * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
+}
+#endif
+#endif
 
 namespace {
 // the instantiation a key names; nullptr: not built
@@ -1323,8 +1386,10 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
                        unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream) {
     if (fp.nloc <= 0) return hipSuccess;
     const bool brute = k.brute != 0, product = !k.count && !k.log, listed = k.acc == kAccListed;
-    const size_t lds = (brute ? brute_lds_bytes(sc, block) : stack_lds_bytes(sc, k.trav, block)) +
-                       (k.smem ? staged_scene_bytes(sc) : 0);
+    // (a brute-force launch: the rules below go by the team kernel's bytes, as they did when every brute-force
+    // kernel staged its tables; the launch takes the bytes of the kernel they end at)
+    size_t lds = (brute ? brute_lds_bytes(sc, block, true) : stack_lds_bytes(sc, k.trav, block)) +
+                 (k.smem ? staged_scene_bytes(sc) : 0);
     hipError_t e = hipSuccess;
     // blocks the device keeps resident of the kernel k names now, at most max_waves waves per SIMD
     auto resident = [&](int max_waves) { return resident_blocks(kernel_fn(k), block, lds, max_waves, &e); };
@@ -1368,6 +1433,7 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     k.ts = f.walk_team;
     if (brute && f.team > 1) k.brute = 2;
     else if (brute) k.brute |= (bslices ? kBruteSliced : 0) | (product && f.refill > 1 ? kBruteRefill : 0);
+    if (brute && f.team <= 1) lds = brute_lds_bytes(sc, block, false);
     const void* fn = kernel_fn(k);
     // the grid stays within what the device keeps resident (not that the slices' hand-off needs it: a job is only
     // held by a running wave, and a pixel's slice k is taken before its slice k + 1)
@@ -1382,6 +1448,9 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     const int shell = (k.brute & 3) == 3 && sc.shell != 0;
     note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f,
                  shell && (sc.host_flags & kHostQuad) != 0});
+#if RT_CHAIN_STAMPS
+    if (!d_counts) d_counts = chain_stamp_buffer();   // (nullptr when the allocation failed: the kernel then adds nothing)
+#endif
     DevScene a0 = sc;
     void* args[] = {&a0, &f, &d_out, &d_counts, &d_work, &lc};
     return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);
