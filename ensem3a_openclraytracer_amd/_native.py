@@ -37,7 +37,7 @@ EXPORTED = (
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
     "rt_trace", "rt_trace_device",
-    "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_scene_info", "rt_debug_pixel_log",
+    "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_trace_clustered", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
     "rt_debug_brute_slices",
@@ -202,6 +202,7 @@ def lib():
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_fn": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
+            "rt_debug_trace_clustered": (_i32, [_c_p, _c_p, _c_p, _i64, _c_p]),
             "rt_debug_scene_info": (_i32, [_c_p, _c_p]),
             "rt_debug_timings": (_i32, [_c_p, _c_p]),
             "rt_debug_wave_counts": (_i32, [_c_p, _c_p, _c_p, _i64, _i32, _i32, _c_p]),
@@ -576,6 +577,16 @@ class Context:
         out = np.zeros(2 * (r.size // 6), dtype=np.float32)
         self._check(lib().rt_debug_trace(self.handle, int(traversal), ptr(r), out.ctypes.data, r.size // 6))
         return out.reshape(-1, 2)
+
+    def debug_trace_clustered(self, rays6):
+        """rt_debug_trace_clustered: the clustered product trace on ``rays6`` (float32[n, 6]: dir, origin), one ray
+        per lane.  Returns (k float32[n], tri int32[n] with -1 for a miss, info int32[4]: clusters, shell, floor,
+        split walls -- what the kernel walked).  Raises NativeError on a scene without clusters."""
+        r = f32(rays6).reshape(-1, 6)
+        out = np.zeros((len(r), 2), dtype=np.float32)
+        info = np.zeros(4, dtype=np.int32)
+        self._check(lib().rt_debug_trace_clustered(self.handle, r.ctypes.data, out.ctypes.data, len(r), info.ctypes.data))
+        return out[:, 0].copy(), out[:, 1].copy().view(np.int32), info
 
     def debug_pixel_log(self, traversal, cam, env, npix, spp, max_bounce, pixel, cap=4096):
         c, e = f32(cam), f32(env)

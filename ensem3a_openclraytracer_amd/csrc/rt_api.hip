@@ -1786,6 +1786,26 @@ int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, in
     return RT_OK;
 }
 
+int rt_debug_trace_clustered(rt_ctx* ctx, const float* rays, float* out, int64_t n, int32_t info[4]) {
+    if (!ctx || !rays || !out || !info || n < 0) return set_err(ctx, RT_ERR_ARG, "bad arguments");
+    if (!ctx->have_scene) return set_err(ctx, RT_ERR_STATE, "no scene");
+    // no fall-back to another trace: the hook runs the clustered loop or nothing
+    if (ctx->hs.nbrute <= 0 || ctx->hs.ncluster <= 0)
+        return set_err(ctx, RT_ERR_ARG, "the scene has no clustered brute-force array (%d records, %d clusters; option "
+                       "\"brute_cluster\" %d)", (int)ctx->hs.nbrute, (int)ctx->hs.ncluster, ctx->brute_cluster);
+    Device& d = ctx->devs[0];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, (size_t)n * 6 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, (size_t)n * 2 * sizeof(float)));
+    if (n) HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, d.stream));
+    HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    HIP_OR_RET(ctx, rt::launch_debug_trace_clustered(dev_scene(ctx, d), (const float*)d.scratch_a.p,
+                                                     (float*)d.scratch_b.p, n, info, d.stream));
+    if (n) HIP_OR_RET(ctx, hipMemcpyAsync(out, d.scratch_b.p, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
 int rt_debug_pixel_log(rt_ctx* ctx, int traversal, const float cam[10], const float env[5], int64_t npix, int spp,
                        int max_bounce, int64_t pixel, float* log, int cap, int* n_events, float out3[3]) {
     rt::FrameParams fp;

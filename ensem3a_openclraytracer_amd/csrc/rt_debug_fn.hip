@@ -1,7 +1,8 @@
 // Test hook rt_debug_fn (rt_debug.h): the shading and hit functions of rt_device.h -- the ones the render
 // kernels call, from the same header -- evaluated one call per item on chosen inputs, so that the tests can
-// compare each of them with the CPU oracle's function instead of through whole frames.  No render kernel
-// lives here and none is changed by this file.
+// compare each of them with the CPU oracle's function instead of through whole frames; and the clustered
+// brute-force trace on the caller's rays (rt_debug_trace_clustered).  No render kernel lives here and none is
+// changed by this file.
 #include "../../include/rt_debug.h"
 #include "rt_device.h"
 
@@ -131,7 +132,58 @@ __global__ void debug_box_fast_kernel(const float* __restrict__ in, float* __res
     out[3 * i + 2] = tmax;
 }
 
+// rt_debug_trace_clustered: the clustered product trace -- trace_brute_compact<false, true> itself, the function
+// render_kernel's BRUTE == 3 instantiations call -- on the caller's rays, one ray per lane.  The block stages what
+// that trace reads from LDS as render_kernel's prologue does: the waves' areas (BRUTE_WAVE_LDS each) | the records'
+// last three float4 (stride 3) | the slots of brute_cbox, with the shell's rows behind them at boxrec + S.shell.
+// Lanes past n leave after the staging, so the last wave of a launch is a partial one, as in a frame's tail.
+__global__ void __launch_bounds__(256) debug_trace_clustered_kernel(DevScene S, const float* __restrict__ rays,
+                                                                    float* __restrict__ out, int64_t n) {
+    extern __shared__ int lds_stack[];
+    const int B = blockDim.x;
+    float4* lr = reinterpret_cast<float4*>(reinterpret_cast<char*>(lds_stack) + (B / 64) * BRUTE_WAVE_LDS);
+    float4* lc = lr + 3 * S.nbrute;
+    for (int q = threadIdx.x; q < 3 * S.nbrute; q += B) lr[q] = S.brute[4 * (q / 3) + 1 + q % 3];
+    for (int q = threadIdx.x; q < 2 * S.ncslot; q += B) lc[q] = S.brute_cbox[q];
+    if (S.shell)
+        for (int q = threadIdx.x; q < 2 * kShellRows; q += B) lc[S.shell + q] = S.brute_cbox[S.shell + kShellRowF4 + q];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * B + threadIdx.x;
+    if (i >= n) return;
+    const float* r = rays + 6 * i;
+    Cnt c{};
+    const Hit h = trace_brute_compact<false, true>(S, ld3(r + 3), ld3(r), reinterpret_cast<char*>(lds_stack) +
+                                                                          (threadIdx.x >> 6) * BRUTE_WAVE_LDS,
+                                                   lr, 3u, c, 1, lc);
+    out[2 * i] = h.k;
+    out[2 * i + 1] = __int_as_float(h.tri);
+}
+
 }  // namespace
+
+// What debug_trace_clustered_kernel stages (above); brute_lds_bytes' terms without the shading tables
+static size_t debug_clustered_lds_bytes(const DevScene& sc, int block) {
+    return (size_t)(block / 64) * BRUTE_WAVE_LDS + (size_t)sc.nbrute * 48 + (size_t)sc.ncslot * 32 +
+           (sc.shell ? (size_t)kShellRows * 32 : 0);
+}
+
+hipError_t launch_debug_trace_clustered(const DevScene& sc, const float* rays, float* out, int64_t n, int32_t info[4],
+                                        hipStream_t stream) {
+    const int block = 256;
+    const size_t lds = debug_clustered_lds_bytes(sc, block);
+    // (the caller refuses a scene without clusters with a message of its own; the staged scene must fit a block)
+    if (sc.nbrute <= 0 || sc.ncluster <= 0 || lds > 64 * 1024 || n > (int64_t)INT_MAX * block) return hipErrorInvalidValue;
+    // what the kernel walks, as launch_pick notes it for a render launch (rt_debug_last_launch out[17..19])
+    const int shell = sc.shell != 0;
+    info[0] = sc.ncluster;
+    info[1] = shell;
+    info[2] = shell && sc.near_floor != 0.0f;
+    info[3] = shell && (sc.host_flags & kHostQuad) != 0;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(debug_trace_clustered_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds, stream,
+                       sc, rays, out, n);
+    return hipGetLastError();
+}
 
 size_t debug_fn_scratch_bytes(int fn, int64_t n) {
     // hemi: tri_shade (n float4) | frames (3 n float4) | two material rows

@@ -369,5 +369,10 @@ constexpr int debug_fn_out(int fn) {
 size_t debug_fn_scratch_bytes(int fn, int64_t n);
 hipError_t launch_debug_fn(const DevScene& sc, int fn, const float* in, float* out, int64_t n, void* scratch,
                            hipStream_t stream);
+// rt_debug_trace_clustered (rt_debug.h; the kernel in rt_debug_fn.hip's translation unit): the clustered product trace
+// over n device rays of rt_debug_trace's layout, 256 lanes per block; info: what the kernel walks (clusters, shell,
+// floor, split walls).  hipErrorInvalidValue for a scene that is not clustered or does not fit a block's LDS.
+hipError_t launch_debug_trace_clustered(const DevScene& sc, const float* rays, float* out, int64_t n, int32_t info[4],
+                                        hipStream_t stream);
 
 }  // namespace rt

@@ -60,6 +60,18 @@ int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* ou
  * triangle index (-1 = miss). */
 int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, int64_t n);
 
+/* Trace n rays (the layout above; the direction is used as given) through the uploaded scene with the clustered
+ * brute-force trace of the one-lane product kernels on device 0 -- the device function those kernels call, not a
+ * restatement of it: one ray per lane in blocks of 256, the scene staged in LDS as the render kernel stages it, the
+ * last wave partial when n is no multiple of 64.  The options "brute_cluster", "brute_shell", "brute_near" and
+ * "brute_quad" act as on a render launch.  out[2*i] = k (1000 on a miss), out[2*i+1] = the bits of the triangle
+ * index (-1 = miss).  info: what the kernel walked, as rt_debug_last_launch reports it for a frame: info[0] =
+ * clusters, info[1] = 1 when it walked a shell, info[2] = 1 when that shell's floor was not zero, info[3] = 1 when
+ * the shell's record has split walls.  RT_ERR_ARG, with a text in rt_last_error, when the uploaded scene has no
+ * clustered array (too many triangles for the brute force, or "brute_cluster" left it unclustered): there is no
+ * fall-back to another trace. */
+int rt_debug_trace_clustered(rt_ctx* ctx, const float* rays, float* out, int64_t n, int32_t info[4]);
+
 /* Evaluate one of the render kernels' own shading and hit functions (rt_device.h: the functions the kernels
  * call, not restatements of them) once per item on device 0.  in holds n items of the function's input
  * floats, out receives n items of its output floats; words marked "bits" carry a 32-bit integer's bit pattern.
