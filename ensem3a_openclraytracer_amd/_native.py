@@ -40,6 +40,7 @@ EXPORTED = (
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_trace_clustered", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
+    "rt_debug_brute_direct", "rt_debug_last_direct", "rt_debug_shell_word",
     "rt_debug_brute_slices",
     "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
@@ -588,6 +589,13 @@ class Context:
         self._check(lib().rt_debug_trace_clustered(self.handle, r.ctypes.data, out.ctypes.data, len(r), info.ctypes.data))
         return out[:, 0].copy(), out[:, 1].copy().view(np.int32), info
 
+    def shell_word(self) -> int:
+        """rt_debug_shell_word: the count word of the uploaded shell record (faces | split faces << 8 | SHELL_DIRECT
+        when option "brute_direct" is on), 0 without a shell."""
+        fn = lib().rt_debug_shell_word
+        fn.restype, fn.argtypes = _i32, [_c_p]
+        return int(fn(self.handle))
+
     def debug_pixel_log(self, traversal, cam, env, npix, spp, max_bounce, pixel, cap=4096):
         c, e = f32(cam), f32(env)
         log = np.zeros((cap, 16), np.float32)
@@ -767,6 +775,34 @@ def brute_quad(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: 
         raise NativeError(st, host_lib().rt_scene_last_error().decode(errors="replace"))
     return dict(split=(flags & 1).astype(bool), side=((flags >> 1) & 1).astype(bool), lines=lines.reshape(6, 4),
                 words=words.view(np.uint32).reshape(6, 3), recs=recs.reshape(6, 2, 3, 3), guard=guard, nfaces=int(info[0]), nsplit=int(info[1]))
+
+
+SHELL_DIRECT = 1 << 16   # rt_layout.h kShellDirect: option "brute_direct" in the shell record's count word
+
+
+def brute_direct(V_p, V_n, faceData, materialData, bvh, cluster: int = -1, shell: int = -1, direct: int = -1,
+                 layout: int = RT_BVH_SAH):
+    """rt_debug_brute_direct (include/rt_debug.h), on the host alone: ``(nfaces, on, word)`` -- the faces of the shell
+    of brute_shell(cluster, shell) (0: none), whether its record carries option "brute_direct"'s bit, and the record's
+    count word as the kernels load it (0 without a shell)."""
+    vp, vn, face, mat, b = f32(V_p), f32(V_n), i32(faceData), f32(materialData), f32(bvh)
+    H = host_lib()
+    fn = H.rt_debug_brute_direct   # (bound here: a library from before the option still loads)
+    fn.restype, fn.argtypes = _i32, [_c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _c_p, _i64, _i32, _i32, _i32, _i32, _c_p]
+    info = np.zeros(3, np.int64)
+    st = fn(ptr(vp), vp.size, ptr(vn), vn.size, ptr(face), face.size, ptr(mat), mat.size, ptr(b), b.size, int(layout),
+            int(cluster), int(shell), int(direct), info.ctypes.data)
+    if st != 0:
+        raise NativeError(st, H.rt_scene_last_error().decode(errors="replace"))
+    return int(info[0]), bool(info[1]), int(info[2])
+
+
+def last_direct() -> bool:
+    """rt_debug_last_direct: whether the last render launch's kernel walked a shell whose record enables the in-place
+    test of a lane's first record (option "brute_direct")."""
+    fn = lib().rt_debug_last_direct
+    fn.restype, fn.argtypes = _i32, []
+    return bool(fn())
 
 
 def brute_slices(nloc: int, lanes: int, spp: int, option: int = -1, accum_base: int = -1):

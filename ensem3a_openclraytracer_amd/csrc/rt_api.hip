@@ -137,6 +137,7 @@ struct rt_ctx {
     int brute_cluster = -1;  // brute force: clustered leaf boxes (0 off, 1 force, -1 auto; option "brute_cluster")
     int brute_shell = -1;    // ... and the shell among their single slots (0 off, 1 force, -1 auto; option "brute_shell")
     int brute_near = -1;     // ... whose face tests take the packer's floor (0 off, -1 or 1 auto; option "brute_near")
+    int brute_direct = -1;   // ... and whose one queue step tests a lane's first record in place (0 off, -1 or 1 auto; option "brute_direct")
     int brute_quad = -1;     // ... and whose split walls queue one record (0 off, -1 or 1 auto; option "brute_quad")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
@@ -328,7 +329,8 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.ncluster = ctx->hs.ncluster;
     s.ncslot = (int32_t)(ctx->hs.brute_cbox.size() / 8);
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
-    s.host_flags = (ctx->brute_cluster < 0 ? rt::kHostClusterAuto : 0) | (ctx->hs.nquad > 0 ? rt::kHostQuad : 0);
+    s.host_flags = (ctx->brute_cluster < 0 ? rt::kHostClusterAuto : 0) | (ctx->hs.nquad > 0 ? rt::kHostQuad : 0) |
+                   (ctx->hs.nshell > 0 && ctx->brute_direct != 0 ? rt::kHostDirect : 0);
     s.nsingle = ctx->hs.nsingle;
     s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
     s.near_floor = s.shell && ctx->brute_near != 0 ? ctx->hs.shell_floor : 0.0f;
@@ -416,7 +418,7 @@ int slot_of(rt_ctx* ctx, int device_index, Device** d, const char* what = "devic
     return RT_OK;
 }
 
-// The options that pack the scene again ("bvh", "brute_max", "brute_cluster", "brute_shell", "brute_quad"): the FAST layout of
+// The options that pack the scene again ("bvh", "brute_max", "brute_cluster", "brute_shell", "brute_quad", "brute_direct"): the FAST layout of
 // the current scene from the values as they are now, on every slot.  Without a scene there is nothing to do.
 int repack_scene(rt_ctx* ctx) {
     if (!ctx->have_scene) return RT_OK;
@@ -424,6 +426,7 @@ int repack_scene(rt_ctx* ctx) {
     std::string why;
     rt::pack_checked(hs, hs.bvh9.data(), hs.nbvh9, hs.ntri, ctx->bvh_layout, ctx->brute_max, ctx->brute_cluster,
                      ctx->brute_shell, ctx->brute_quad, why);
+    rt::shell_direct(hs, ctx->brute_direct);
     for (auto& d : ctx->devs) {
         const int st = upload_fast(ctx, d, hs);
         if (st) return st;
@@ -477,6 +480,8 @@ const std::vector<Option>& options() {
         {"brute_near", &rt_ctx::brute_near, range(-1, 1), "brute_near must be -1 (auto), 0 (off) or 1 (auto)", none},
         // the lines and the enable ride in the shell's record (no DevScene field): packed and uploaded again
         {"brute_quad", &rt_ctx::brute_quad, range(-1, 1), "brute_quad must be -1 (auto), 0 (off) or 1 (auto)", repack},
+        // the enable rides in the shell's record too (rt_layout.h kShellDirect)
+        {"brute_direct", &rt_ctx::brute_direct, range(-1, 1), "brute_direct must be -1 (auto), 0 (off) or 1 (auto)", repack},
         {"bvh", &rt_ctx::bvh_layout, range(RT_BVH_REFERENCE, RT_BVH_SAH), "bvh must be 0 (reference tree) or 1 (sah)", repack},
         {"brute_cluster", &rt_ctx::brute_cluster, range(-1, 1), "brute_cluster must be -1 (auto), 0 (off) or 1 (force)", repack},
         {"brute_shell", &rt_ctx::brute_shell, range(-1, 1), "brute_shell must be -1 (auto), 0 (off) or 1 (force)", repack},
@@ -591,6 +596,7 @@ int rt_set_scene(rt_ctx* ctx, const float* vp, int64_t nvp, const float* vn, int
     const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, ctx->bvh_layout,
                                      ctx->brute_max, ctx->brute_cluster, ctx->brute_shell, ctx->brute_quad, msg, why);
     if (rc != RT_OK) return set_err(ctx, rc, "%s", msg.c_str());
+    rt::shell_direct(hs, ctx->brute_direct);
     invalidate_accum(ctx);
     const auto t1 = std::chrono::steady_clock::now();
     for (auto& d : ctx->devs) {
@@ -1854,6 +1860,15 @@ int rt_debug_brute_slices(int64_t nloc, int64_t lanes, int spp, int option, int 
 }
 
 int rt_debug_last_slices(void) { return rt::last_launch().slices; }
+
+int rt_debug_last_direct(void) { return rt::last_launch().direct; }
+
+int rt_debug_shell_word(rt_ctx* ctx) {
+    if (!ctx || !ctx->have_scene || ctx->hs.nshell <= 0 || ctx->hs.brute_shell.size() < 8) return 0;
+    int32_t w;
+    std::memcpy(&w, &ctx->hs.brute_shell[7], sizeof w);
+    return w;
+}
 
 int rt_debug_last_launch(int32_t out[20]) {
     if (!out) return RT_ERR_ARG;

@@ -135,15 +135,15 @@ __global__ void debug_box_fast_kernel(const float* __restrict__ in, float* __res
 // rt_debug_trace_clustered: the clustered product trace -- trace_brute_compact<false, true> itself, the function
 // render_kernel's BRUTE == 3 instantiations call -- on the caller's rays, one ray per lane.  The block stages what
 // that trace reads from LDS as render_kernel's prologue does: the waves' areas (BRUTE_WAVE_LDS each) | the records'
-// last three float4 (stride 3) | the slots of brute_cbox, with the shell's rows behind them at boxrec + S.shell.
+// copy (stage_mt_records, stride 3) | the slots of brute_cbox, with the shell's rows behind them at boxrec + S.shell.
 // Lanes past n leave after the staging, so the last wave of a launch is a partial one, as in a frame's tail.
 __global__ void __launch_bounds__(256) debug_trace_clustered_kernel(DevScene S, const float* __restrict__ rays,
                                                                     float* __restrict__ out, int64_t n) {
-    extern __shared__ int lds_stack[];
+    extern __shared__ __attribute__((aligned(16))) int lds_stack[];
     const int B = blockDim.x;
     float4* lr = reinterpret_cast<float4*>(reinterpret_cast<char*>(lds_stack) + (B / 64) * BRUTE_WAVE_LDS);
     float4* lc = lr + 3 * S.nbrute;
-    for (int q = threadIdx.x; q < 3 * S.nbrute; q += B) lr[q] = S.brute[4 * (q / 3) + 1 + q % 3];
+    stage_mt_records(lr, S.brute, S.nbrute);
     for (int q = threadIdx.x; q < 2 * S.ncslot; q += B) lc[q] = S.brute_cbox[q];
     if (S.shell)
         for (int q = threadIdx.x; q < 2 * kShellRows; q += B) lc[S.shell + q] = S.brute_cbox[S.shell + kShellRowF4 + q];

@@ -523,6 +523,28 @@ __device__ __forceinline__ unsigned quad_pick(float4 ln, float4 wd, rtm_f3 o, rt
     return __float_as_uint(sure ? (sg >= 0.0f ? wd.y : wd.z) : wd.x);
 }
 
+// The LDS copy of the brute-force records, as the MT batches read it (trace_brute_compact LREC; staged by
+// render_kernel's prologue and debug_trace_clustered_kernel's, priced by brute_lds_bytes at 48 bytes a record):
+// from the last three float4 of a global record -- hi.y hi.z a.x a.y | a.z e1.xyz | e2.xyz tri -- the copy keeps
+// a.xyz e1.x | e1.yz e2.xy | e2.z tri - -, so that the two float4 a batch reads hold nothing it does not use and
+// are read as 16 bytes each (with the two dead words in front the compiler narrowed the reads to 8 + 4 + 8 bytes).
+// The stride stays 3 float4; the wave areas and the tables behind them are multiples of 16 bytes, and the kernels
+// declare the dynamic LDS array 16-byte aligned.  Record numbers are the global array's
+#ifndef RT_WIDE_REC
+#define RT_WIDE_REC 1   // 0: an A/B build whose copy keeps the global record's three float4 (and the ring's step for
+                        // every record: the in-place test reads the new copy)
+#endif
+static_assert(BRUTE_WAVE_LDS % 16 == 0 && BRUTE_INV_OFF % 16 == 0 && BRUTE_STAMP_OFF % 16 == 0, "16-byte LDS tables");
+__device__ __forceinline__ void stage_mt_records(float4* lr, const float4* brute, int nbrute) {
+    for (int q = threadIdx.x; q < nbrute; q += blockDim.x) {
+        const float4 g1 = brute[4 * q + 1], g2 = brute[4 * q + 2], g3 = brute[4 * q + 3];
+        if (!RT_WIDE_REC) { lr[3 * q] = g1; lr[3 * q + 1] = g2; lr[3 * q + 2] = g3; continue; }
+        lr[3 * q] = make_float4(g1.z, g1.w, g2.x, g2.y);
+        lr[3 * q + 1] = make_float4(g2.z, g2.w, g3.x, g3.y);
+        lr[3 * q + 2] = make_float4(g3.z, g3.w, 0.0f, 0.0f);
+    }
+}
+
 // a width of the lock-step walk's pieces, as a type (trace_brute_compact)
 template <int N> struct IntC { static constexpr int value = N; };
 static_assert(kBoxGroup == 1 || kBoxGroup == 2 || kBoxGroup == 4 || kBoxGroup == 8, "the lock-step tail is cut into powers of two");
@@ -544,9 +566,12 @@ static_assert(kBoxGroup == 1 || kBoxGroup == 2 || kBoxGroup == 4 || kBoxGroup ==
 // bestk: never behind the owner's own bk), and queues the slot's records for the owner like a lock-step pass.
 // The tests a ray's boxes get, and the triangles it is tested against, are those of the lock-step loop up
 // to culling, which changes no hit.
-template <bool COUNT, bool CLU = false>
+// LREC: mtrec is the LDS copy of the records in the batches' own layout (mt_pair below; the prologues that stage it:
+// stage_mt_records), which the clustered kernels always have; otherwise the global records (mtstride 4)
+template <bool COUNT, bool CLU = false, bool LREC_ = CLU>
 __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* wl, const float4* mtrec,
                                    unsigned mtstride, Cnt& c, int ts = 1, const float4* boxrec = nullptr) {
+    constexpr bool LREC = LREC_ && RT_WIDE_REC;
     const unsigned lane = threadIdx.x & 63;
     const unsigned sub = lane & (unsigned)(ts - 1), tl = lane - sub;   // lane in team, team leader
     if (COUNT && sub == 0) c.rays++;
@@ -565,6 +590,27 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
     float bk = 1000.0f;
     unsigned head = 0, tail = 0;   // wave-uniform ring positions
     [[maybe_unused]] int sec = kStampShell;   // (RT_CHAIN_STAMPS: the section the wave is in)
+    // record q of the LDS copy (LREC, stride 3: a.xyz e1.x | e1.yz e2.xy | e2.z tri - -, every dword of the two float4
+    // one the test uses, so they are two 16-byte reads and a 4-byte one; r21) against the ray ro, rd: the
+    // Moller-Trumbore test of a batch's pair, and of the shell step's first record, which a lane tests in place
+    // with its own o, d -- one text, so k has the same bits either way
+    [[maybe_unused]] auto mt_pair = [&](const rtm_f3 ro, const rtm_f3 rd, unsigned q, float& k) __attribute__((always_inline)) {
+        const float4* rq = mtrec + mtstride * q;
+        const float4 r1 = rq[0], r2 = rq[1];
+        const float r3 = reinterpret_cast<const float*>(rq)[8];
+        const rtm_f3 a = rtm_v3(r1.x, r1.y, r1.z), e1 = rtm_v3(r1.w, r2.x, r2.y), e2 = rtm_v3(r2.z, r2.w, r3);
+        const rtm_f3 h = rtm_cross(rd, e2);
+        const float det = rtm_dot(e1, h);
+        const float f = mt_recip(det);
+        const rtm_f3 sv = rtm_sub(ro, a);
+        const float u = f * rtm_dot(sv, h);
+        const rtm_f3 qv = rtm_cross(sv, e1);
+        const float v = f * rtm_dot(rd, qv);
+        k = f * rtm_dot(e2, qv);
+        const bool parallel = det > -0.0000001f && det < 0.0000001f;
+        return !parallel && !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) &&
+               (k > 0.0000001f) && k > 0.0001f && k < 1000.0f;
+    };
     auto run_batch = [&](int n) __attribute__((always_inline)) {
         if constexpr (CLU && !COUNT) chain_stamp(wl, sec);
         if (myrank < n) {
@@ -572,22 +618,29 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             const unsigned ow = e >> 16, q = e & 0xffffu;
             const rtm_f3 ro = rtm_v3(ray[ow], ray[64 + ow], ray[128 + ow]);
             const rtm_f3 rd = rtm_v3(ray[192 + ow], ray[256 + ow], ray[320 + ow]);
-            // record q's last three float4 (hi.yz a.xy | a.z e1.xyz | e2.xyz tri): LDS copy or global
-            const float4* rq = mtrec + mtstride * q;
-            const float4 r1 = rq[0], r2 = rq[1], r3 = rq[2];
-            const rtm_f3 a = rtm_v3(r1.z, r1.w, r2.x), e1 = rtm_v3(r2.y, r2.z, r2.w), e2 = rtm_v3(r3.x, r3.y, r3.z);
-            const rtm_f3 h = rtm_cross(rd, e2);
-            const float det = rtm_dot(e1, h);
-            const float f = mt_recip(det);
-            const rtm_f3 sv = rtm_sub(ro, a);
-            const float u = f * rtm_dot(sv, h);
-            const rtm_f3 qv = rtm_cross(sv, e1);
-            const float v = f * rtm_dot(rd, qv);
-            const float k = f * rtm_dot(e2, qv);
-            const bool parallel = det > -0.0000001f && det < 0.0000001f;
-            const bool hit = !parallel && !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) &&
-                             (k > 0.0000001f) && k > 0.0001f && k < 1000.0f;
-            if (hit) atomicMin(&bestk[ow], ((unsigned long long)__float_as_uint(k) << 32) | q);
+            if constexpr (LREC) {
+                float k;
+                if (mt_pair(ro, rd, q, k)) atomicMin(&bestk[ow], ((unsigned long long)__float_as_uint(k) << 32) | q);
+            } else {
+                // the global record's last three float4 (hi.yz a.xy | a.z e1.xyz | e2.xyz tri), in the text this path
+                // has always had: the kernels that read the global records (the queries, the tree walks' fall-back)
+                // compile to the code they were
+                const float4* rq = mtrec + mtstride * q;
+                const float4 r1 = rq[0], r2 = rq[1], r3 = rq[2];
+                const rtm_f3 a = rtm_v3(r1.z, r1.w, r2.x), e1 = rtm_v3(r2.y, r2.z, r2.w), e2 = rtm_v3(r3.x, r3.y, r3.z);
+                const rtm_f3 h = rtm_cross(rd, e2);
+                const float det = rtm_dot(e1, h);
+                const float f = mt_recip(det);
+                const rtm_f3 sv = rtm_sub(ro, a);
+                const float u = f * rtm_dot(sv, h);
+                const rtm_f3 qv = rtm_cross(sv, e1);
+                const float v = f * rtm_dot(rd, qv);
+                const float k = f * rtm_dot(e2, qv);
+                const bool parallel = det > -0.0000001f && det < 0.0000001f;
+                const bool hit = !parallel && !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) &&
+                                 (k > 0.0000001f) && k > 0.0001f && k < 1000.0f;
+                if (hit) atomicMin(&bestk[ow], ((unsigned long long)__float_as_uint(k) << 32) | q);
+            }
         }
         head += n;
         wave_lds_sync();
@@ -699,7 +752,9 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
             const ConstF4 sh{cb.p + 4 * S.shell};
             const float4 h0 = sgpr4(sh[0]), h1 = sgpr4(sh[1]), fx = sgpr4(sh[2]), fy = sgpr4(sh[3]), fz = sgpr4(sh[4]);
             // split walls in the record (above the face count; 0: option "brute_quad" is off or nothing to split)
-            const int nquad = __float_as_int(h1.w) >> 8;
+            const int nquad = (__float_as_int(h1.w) >> 8) & 0xff;
+            // ... and the enable of the first record's in-place test (kShellDirect; option "brute_direct")
+            [[maybe_unused]] const bool direct = (__float_as_int(h1.w) & kShellDirect) != 0;
             const float cull = bk * CULL_MARGIN, nearf = S.near_floor;
             const float x0 = (h0.x - o.x) * ix, x1 = (h0.y - o.x) * ix;
             const float y0 = (h0.z - o.y) * iy, y1 = (h0.w - o.y) * iy;
@@ -766,7 +821,37 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
                 }
                 const bool p1 = pk != ~0u, p2 = pk < 0xffff0000u;
                 const unsigned long long m1 = __ballot(p1);
-                if (m1 != 0) {
+                // The first record tested in place (r21, option "brute_direct": a bit of the record's count word).
+                // Nearly every tracing lane has exactly one first record here, so the ring compacts nothing: the lane
+                // tests record pk & 0xffff itself with the o and d it holds -- mt_pair, the batch's own arithmetic,
+                // so k has the batch's bits -- and only the second records go to the ring, by the rule above.  A lane
+                // without a face (pk == ~0u, an open side) tests record 0 and drops the result: no exec-mask change.
+                // Nothing has been queued before this step (it is the trace's first: head == tail == 0), so
+                // bestk[lane] still holds nokey and the lane's key is stored, not minimised (ts == 1: tl == lane);
+                // batches that run later minimise against it as before, and bk is the lane's own k, not read back.
+                // The ring's bound: nothing is queued before the step and a lane adds at most 1, 64 in all, under
+                // the ring's 256.  The order argument is the one above: the first records' keys reach bestk before
+                // any batch instead of in the first one, the second records' batches run later or in the tail,
+                // and a later cull sees another bk -- some accepted k of the lane's, as ever, so never below its hit's:
+                // bestk is an atomic minimum over (k, record) keys and a cull changes no hit.  The instrumented
+                // kernels keep the ring's step
+                if (LREC && !COUNT && direct && m1 != 0) {
+                    const unsigned q1 = p1 ? (pk & 0xffffu) : 0u;
+                    float k1;
+                    const bool hit1 = mt_pair(o, d, q1, k1) && p1;
+                    bestk[lane] = hit1 ? ((unsigned long long)__float_as_uint(k1) << 32) | q1 : nokey;
+                    bk = hit1 ? k1 : bk;
+                    const unsigned long long m2 = __ballot(p2);
+                    if (m2 != 0) {
+                        ring[p2 ? (lane_prefix(m2, tail) & (BRUTE_RING - 1)) : BRUTE_RING + lane] = (tl << 16) | (pk >> 16);
+                        tail += (unsigned)__popcll(m2);
+                    }
+                    wave_lds_sync();
+                    if ((int)(tail - head) >= nact) {
+                        do run_batch(nact); while ((int)(tail - head) >= nact);
+                        bk = __uint_as_float((unsigned)(bestk[tl] >> 32));
+                    }
+                } else if (m1 != 0) {
                     const unsigned long long m2 = __ballot(p2);
                     const unsigned n1 = (unsigned)__popcll(m1);
                     if (COUNT && p1) c.tris += p2 ? 2 : 1;
@@ -915,7 +1000,8 @@ __device__ Hit trace_brute_compact(const DevScene& S, rtm_f3 o, rtm_f3 d, char* 
     if (key != nokey) {
         best.k = __uint_as_float((unsigned)(key >> 32));
         // triangle index: the record's last float4 (read from the LDS copy when it is staged)
-        best.tri = __float_as_int(mtrec[mtstride * (unsigned)(key & 0xffffffffu) + 2].w);
+        const float4* rq = mtrec + mtstride * (unsigned)(key & 0xffffffffu);
+        best.tri = __float_as_int(LREC ? reinterpret_cast<const float*>(rq)[9] : rq[2].w);
     }
     if constexpr (CLU && !COUNT) chain_stamp(wl, kStampTail);
     return best;
@@ -931,7 +1017,7 @@ __device__ __forceinline__ Hit trace(const DevScene& S, const float4* nodes, con
                                      int ts = 1, const float4* boxrec = nullptr) {
     if (TRAV == TRAV_REF) return trace_ref<COUNT>(S, o, d, stk, B, c);
     if (S.nbrute > 0)
-        return trace_brute_compact<COUNT, CLU>(S, o, d, reinterpret_cast<char*>(stk - threadIdx.x) +
+        return trace_brute_compact<COUNT, CLU, BLDS>(S, o, d, reinterpret_cast<char*>(stk - threadIdx.x) +
                                                         (threadIdx.x >> 6) * BRUTE_WAVE_LDS,
                                           BLDS ? mtrec : S.brute + 1, BLDS ? 3u : 4u, c, BLDS ? ts : 1, boxrec);
     return trace_fast<COUNT, SOA, OVF>(S, nodes, tris, o, d, st, c);

@@ -12,6 +12,7 @@ namespace rt {
 // Device view of one uploaded scene (all pointers are device pointers).
 // bits of DevScene::host_flags
 constexpr int32_t kHostClusterAuto = 1;   // option "brute_cluster" is -1: only tiles of at least a pixel per resident lane are clustered
+constexpr int32_t kHostDirect = 4;        // ... and the enable of the in-place test (option "brute_direct"; rt_debug_last_direct)
 constexpr int32_t kHostQuad = 2;          // the shell's record has split faces (option "brute_quad"; rt_debug_last_launch)
 struct DevScene {
     // FAST traversal: BVH2 nodes holding both child boxes, 4 x float4 each:
@@ -346,6 +347,7 @@ struct LaunchNote {
     int shell;   // the kernel walks the scene's shell (the clustered loop, DevScene::shell != 0)
     int near;    // ... with a non-zero floor in its face tests (DevScene::near_floor != 0)
     int quad;    // ... and split faces in its record (option "brute_quad")
+    int direct;  // ... and the in-place test of the first record enabled in it (option "brute_direct")
 };
 void note_launch(const LaunchNote& n);
 LaunchNote last_launch();

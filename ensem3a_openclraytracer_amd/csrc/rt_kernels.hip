@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     static_assert(!SLICED || BRUTE == 1 || BRUTE == 3, "sample slices: the one-lane brute-force loops");
     constexpr bool kRefill = (BRUTE == 1 || BRUTE == 3) && ((BRUTE_ & kBruteRefill) != 0 || COUNT || LOG);
     static_assert(!(BRUTE_ & kBruteRefill) || BRUTE == 1 || BRUTE == 3, "refill threshold: the one-lane brute-force loops");
-    extern __shared__ int lds_stack[];
+    extern __shared__ __attribute__((aligned(16))) int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
     const LaneStack lst = lane_stack(S, lds_stack);
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         }
         float4* lf = ls + (ROWS ? 2 : 1) * S.ntri;
         float* lm = reinterpret_cast<float*>(lf + 3 * S.ntri);
-        for (int q = threadIdx.x; q < 3 * S.nbrute; q += B) lr[q] = S.brute[4 * (q / 3) + 1 + q % 3];
+        stage_mt_records(lr, S.brute, S.nbrute);   // (rt_device.h: the batches' own layout)
         for (int q = threadIdx.x; q < 3 * S.ntri; q += B) lf[q] = S.tri_frame[q];
         if constexpr (ROWS) {
             for (int q = threadIdx.x; q < S.ntri; q += B) {
@@ -1447,7 +1447,7 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     if (e != hipSuccess) return e;
     const int shell = (k.brute & 3) == 3 && sc.shell != 0;
     note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f,
-                 shell && (sc.host_flags & kHostQuad) != 0});
+                 shell && (sc.host_flags & kHostQuad) != 0, shell && (sc.host_flags & kHostDirect) != 0});
 #if RT_CHAIN_STAMPS
     if (!d_counts) d_counts = chain_stamp_buffer();   // (nullptr when the allocation failed: the kernel then adds nothing)
 #endif

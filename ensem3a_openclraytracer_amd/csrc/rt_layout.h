@@ -54,6 +54,9 @@ constexpr int kShellRows = 7;
 constexpr int kShellRowF4 = 5;                     // where the rows start in the record, in float4
 constexpr int kShellRecF = 20 + 8 * kShellRows;
 constexpr int kShellMinFaces = 3;
+// ... and, above the split faces, the enable of the first record's in-place test (option "brute_direct",
+// scene_pack.cpp shell_direct; rt_device.h trace_brute_compact's one queue step)
+constexpr int32_t kShellDirect = 1 << 16;
 // The one queue step's choice between a split wall's two records (option "brute_quad"; DESIGN.md 4.2 has the proof).
 // A lane is sure of its side sigma~ = A . (o + T d) + gamma of the wall's diagonal, and queues that side's record
 // alone, when the origin lies in the shell's box, kQuadGraze max|d| <= |d_a| for the wall's axis a, max|d| <=

@@ -976,6 +976,13 @@ bool pack_fast(HostScene& hs, const float* bvh9, int64_t nn, int64_t ntri, int l
 
 namespace rt {
 
+bool shell_direct(HostScene& hs, int direct) {
+    if (hs.nshell <= 0 || hs.brute_shell.size() < (size_t)rt::kShellRecF) return false;
+    const int32_t w = as_i32(hs.brute_shell[7]);
+    hs.brute_shell[7] = as_f32(direct != 0 ? (w | rt::kShellDirect) : (w & ~rt::kShellDirect));
+    return direct != 0;
+}
+
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
                   int shell, int quad, std::string& why) {
     hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, shell, quad, why) : true;
@@ -1268,6 +1275,37 @@ extern "C" int rt_debug_brute_near(const float* vp, int64_t nvp, const float* vn
     *floor = hs.shell_floor;
     const int64_t n = std::min<int64_t>(cap, info[0]);
     for (int64_t g = 0; g < n; ++g) flags[g] = hs.brute_near[(size_t)g];
+    return RT_OK;
+}
+
+extern "C" int rt_debug_brute_direct(const float* vp, int64_t nvp, const float* vn, int64_t nvn, const int32_t* face,
+                                     int64_t nface, const float* mat, int64_t nmat, const float* bvh9, int64_t nbvh,
+                                     int layout, int cluster, int shell, int direct, int64_t info[3]) {
+    HostScene hs;
+    std::string msg, why;
+    if (layout != RT_BVH_REFERENCE && layout != RT_BVH_SAH) {
+        g_check_error = "layout must be RT_BVH_REFERENCE or RT_BVH_SAH";
+        return RT_ERR_ARG;
+    }
+    if (cluster < -1 || cluster > 1 || shell < -1 || shell > 1) {
+        g_check_error = "brute_cluster and brute_shell must be -1 (auto), 0 (off) or 1 (force)";
+        return RT_ERR_ARG;
+    }
+    if (direct < -1 || direct > 1) {
+        g_check_error = "brute_direct must be -1 (auto), 0 (off) or 1 (auto)";
+        return RT_ERR_ARG;
+    }
+    if (!info) {
+        g_check_error = "null info";
+        return RT_ERR_ARG;
+    }
+    const int rc = rt::scene_prepare(hs, vp, nvp, vn, nvn, face, nface, mat, nmat, bvh9, nbvh, layout,
+                                     RT_BRUTE_MAX_DEFAULT, cluster, shell, -1, msg, why);
+    g_check_error = rc != RT_OK ? msg : hs.fast_ok ? std::string() : "FAST traversal unavailable (" + why + ")";
+    if (rc != RT_OK) return rc;
+    info[1] = rt::shell_direct(hs, direct) ? 1 : 0;
+    info[0] = hs.nshell;
+    info[2] = hs.nshell > 0 ? (int64_t)as_i32(hs.brute_shell[7]) : 0;
     return RT_OK;
 }
 

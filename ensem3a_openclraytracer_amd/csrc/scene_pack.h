@@ -67,4 +67,9 @@ int scene_prepare(HostScene& hs, const float* vp, int64_t nvp, const float* vn, 
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
                   int shell, int quad, std::string& why);
 
+// Option "brute_direct" (0 off, else auto): the bit kShellDirect of the shell record's count word, set exactly when
+// the option is on and the packed scene has a shell.  The callers of scene_prepare / pack_checked call it after
+// every pack; true when the record carries the bit.
+bool shell_direct(HostScene& hs, int direct);
+
 }  // namespace rt

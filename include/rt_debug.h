@@ -25,6 +25,9 @@
  *                  through queues that side's triangle alone (kQuadBand, kQuadGraze in rt_layout.h; the packer
  *                  splits a wall only where its error bound allows it); packs the scene again (0 off, -1 auto; 1
  *                  means auto: an unsafe wall cannot be forced)
+ *   "brute_direct" clustered brute force with a shell: in the one queue step a lane tests the first record of the
+ *                  wall it leaves through itself, with the ray it holds, and only second records go to the pair
+ *                  queue; packs the scene again (0 off: every record through the queue, -1 auto; 1 means auto)
  *   "brute_refill" brute force, one lane per pixel: a wave hands out jobs once this many lanes are free, 2..64
  *                  (0 or 1 every free lane at once, -1 auto: 4 on tiles of >= 1.5 pixels per resident lane)
  *   "walk_team"    BVH2 walk: lanes walking each ray of a pixel together 1/2/4/8 (0 auto)
@@ -63,8 +66,8 @@ int rt_debug_trace(rt_ctx* ctx, int traversal, const float* rays, float* out, in
 /* Trace n rays (the layout above; the direction is used as given) through the uploaded scene with the clustered
  * brute-force trace of the one-lane product kernels on device 0 -- the device function those kernels call, not a
  * restatement of it: one ray per lane in blocks of 256, the scene staged in LDS as the render kernel stages it, the
- * last wave partial when n is no multiple of 64.  The options "brute_cluster", "brute_shell", "brute_near" and
- * "brute_quad" act as on a render launch.  out[2*i] = k (1000 on a miss), out[2*i+1] = the bits of the triangle
+ * last wave partial when n is no multiple of 64.  The options "brute_cluster", "brute_shell", "brute_near",
+ * "brute_quad" and "brute_direct" act as on a render launch.  out[2*i] = k (1000 on a miss), out[2*i+1] = the bits of the triangle
  * index (-1 = miss).  info: what the kernel walked, as rt_debug_last_launch reports it for a frame: info[0] =
  * clusters, info[1] = 1 when it walked a shell, info[2] = 1 when that shell's floor was not zero, info[3] = 1 when
  * the shell's record has split walls.  RT_ERR_ARG, with a text in rt_last_error, when the uploaded scene has no
@@ -196,6 +199,21 @@ int rt_debug_brute_quad(const float* V_p, int64_t n_vp, const float* V_n, int64_
                         int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
                         int layout, int cluster, int shell, int quad, int32_t flags[6], float lines[24],
                         int32_t words[18], float recs[108], float guard[3], int64_t info[2]);
+
+/* Host-only (no device): option "brute_direct" = direct (-1 auto, 0 off, 1 auto) in the shell of
+ * rt_debug_brute_shell(cluster, shell).  info[0] = faces of the shell (0: none), info[1] = 1 when its record carries
+ * the option's bit -- exactly when the option is not 0 and there is a shell --, info[2] = the record's count word as
+ * the kernels load it: faces | split faces << 8 | the bit << 16 (0 without a shell). */
+int rt_debug_brute_direct(const float* V_p, int64_t n_vp, const float* V_n, int64_t n_vn, const int32_t* faceData,
+                          int64_t n_face, const float* materialData, int64_t n_mat, const float* bvh, int64_t n_bvh,
+                          int layout, int cluster, int shell, int direct, int64_t info[3]);
+
+/* 1 when the kernel of the process's last render launch walked a shell whose record carries that bit, else 0. */
+int rt_debug_last_direct(void);
+
+/* The count word of the shell's record as the context's scene was packed and uploaded with its options now -- what
+ * a render launch's kernel and rt_debug_trace_clustered's load --, 0 when there is no scene or no shell. */
+int rt_debug_shell_word(rt_ctx* ctx);
 
 /* No device call: the rule for sample slices on a brute-force scene (option "slices" = option: -1 auto, 0 off,
  * K) for a launch over a tile of nloc pixels on a device that keeps `lanes` lanes of the kernel resident, which
