@@ -43,7 +43,7 @@ EXPORTED = (
     "rt_debug_brute_direct", "rt_debug_last_direct", "rt_debug_shell_word",
     "rt_debug_brute_slices",
     "rt_debug_last_slices",
-    "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch",
+    "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch", "rt_debug_brute_lean",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
@@ -830,6 +830,23 @@ def brute_refill(nloc: int, lanes: int, option: int = -1) -> int:
     return int(out[0])
 
 
+def brute_lean(materialData, env, spp: int = 4, max_bounce: int = 4, pass_: int = 0, pilot: int = 0,
+               fixed_point: int = 1, sun_cache: int = 1, option: int = -1, loop: int = 3, team: int = 1,
+               count: int = 0, log: int = 0, acc: int = 0, traversal: int = 0):
+    """rt_debug_brute_lean (include/rt_debug.h), on the host alone: ``(diffuse_only, lean)`` -- whether every material
+    of the table has type 0 or 1, and whether a launch of that kernel over such a frame runs the lean kernel."""
+    mat, e = f32(materialData), f32(env)
+    fn = lib().rt_debug_brute_lean   # (bound here: a library from before the option still loads)
+    fn.restype, fn.argtypes = _i32, [_c_p, _i64, _c_p, _c_p, _c_p, _c_p]
+    frame = np.array([spp, max_bounce, pass_, pilot, fixed_point, sun_cache, option], np.int32)
+    kernel = np.array([loop, team, count, log, acc, traversal], np.int32)
+    out = np.zeros(2, np.int32)
+    st = fn(ptr(mat) if mat.size else None, mat.size, ptr(e), frame.ctypes.data, kernel.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_debug_brute_lean: bad arguments")
+    return bool(out[0]), bool(out[1])
+
+
 def last_refill():
     """rt_debug_last_refill: ``(R, events, lanes)`` -- the threshold the last render launch's kernel got, and the
     refill counters of the last instrumented launch."""
@@ -844,6 +861,7 @@ LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide"
                  "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near", "quad")
 BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
 BRUTE_REFILL = 8
+BRUTE_LEAN = 16    # the lean form of the one-lane kernels (option "brute_lean"; rt_debug_brute_lean has the rule)
 
 
 def last_launch() -> dict:

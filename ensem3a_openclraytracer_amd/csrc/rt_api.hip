@@ -138,6 +138,7 @@ struct rt_ctx {
     int brute_shell = -1;    // ... and the shell among their single slots (0 off, 1 force, -1 auto; option "brute_shell")
     int brute_near = -1;     // ... whose face tests take the packer's floor (0 off, -1 or 1 auto; option "brute_near")
     int brute_direct = -1;   // ... and whose one queue step tests a lane's first record in place (0 off, -1 or 1 auto; option "brute_direct")
+    int brute_lean = -1;     // the lean loop for all-diffuse one-shot frames (0 off, -1 or 1 auto; option "brute_lean"; rt_internal.h brute_lean_frame)
     int brute_quad = -1;     // ... and whose split walls queue one record (0 off, -1 or 1 auto; option "brute_quad")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
@@ -330,7 +331,8 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.ncslot = (int32_t)(ctx->hs.brute_cbox.size() / 8);
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
     s.host_flags = (ctx->brute_cluster < 0 ? rt::kHostClusterAuto : 0) | (ctx->hs.nquad > 0 ? rt::kHostQuad : 0) |
-                   (ctx->hs.nshell > 0 && ctx->brute_direct != 0 ? rt::kHostDirect : 0);
+                   (ctx->hs.nshell > 0 && ctx->brute_direct != 0 ? rt::kHostDirect : 0) |
+                   (ctx->hs.diffuse_only && ctx->brute_lean != 0 ? rt::kHostLean : 0);
     s.nsingle = ctx->hs.nsingle;
     s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
     s.near_floor = s.shell && ctx->brute_near != 0 ? ctx->hs.shell_floor : 0.0f;
@@ -482,6 +484,8 @@ const std::vector<Option>& options() {
         {"brute_quad", &rt_ctx::brute_quad, range(-1, 1), "brute_quad must be -1 (auto), 0 (off) or 1 (auto)", repack},
         // the enable rides in the shell's record too (rt_layout.h kShellDirect)
         {"brute_direct", &rt_ctx::brute_direct, range(-1, 1), "brute_direct must be -1 (auto), 0 (off) or 1 (auto)", repack},
+        // the flag reaches launch_pick in DevScene::host_flags, made for every launch: nothing is packed or uploaded
+        {"brute_lean", &rt_ctx::brute_lean, range(-1, 1), "brute_lean must be -1 (auto), 0 (off) or 1 (auto)", none},
         {"bvh", &rt_ctx::bvh_layout, range(RT_BVH_REFERENCE, RT_BVH_SAH), "bvh must be 0 (reference tree) or 1 (sah)", repack},
         {"brute_cluster", &rt_ctx::brute_cluster, range(-1, 1), "brute_cluster must be -1 (auto), 0 (off) or 1 (force)", repack},
         {"brute_shell", &rt_ctx::brute_shell, range(-1, 1), "brute_shell must be -1 (auto), 0 (off) or 1 (force)", repack},
@@ -1884,6 +1888,24 @@ int rt_debug_last_launch(int32_t out[20]) {
 int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out) {
     if (!out || nloc < 0 || lanes < 0 || option < -1 || option > rt::kRefillMax) return RT_ERR_ARG;
     *out = rt::brute_refill_launch(option, nloc, lanes);
+    return RT_OK;
+}
+
+int rt_debug_brute_lean(const float* mat, int64_t nmat6, const float env[5], const int32_t frame[7],
+                        const int32_t kernel[6], int32_t out[2]) {
+    if ((nmat6 > 0 && !mat) || nmat6 < 0 || nmat6 % 6 || !env || !frame || !kernel || !out) return RT_ERR_ARG;
+    if (frame[6] < -1 || frame[6] > 1) return RT_ERR_ARG;
+    out[0] = rt::materials_diffuse_only(mat, nmat6) ? 1 : 0;
+    rt::FrameParams fp{};
+    std::memcpy(fp.env, env, sizeof fp.env);
+    fp.spp = frame[0];
+    fp.max_bounce = frame[1];
+    fp.pass = frame[2];
+    fp.pilot = frame[3];
+    fp.fixed_point = frame[4];
+    fp.sun_cache = frame[4] && frame[5] ? 1 : 0;   // (as check_frame makes it)
+    rt::KernelKey k{kernel[5], kernel[2], kernel[3], 0, 0, 0, 1, 0, kernel[0], 1, kernel[4]};
+    out[1] = rt::brute_lean_kernel(k, kernel[1]) && rt::brute_lean_frame(out[0] && frame[6] != 0 ? rt::kHostLean : 0, fp);
     return RT_OK;
 }
 

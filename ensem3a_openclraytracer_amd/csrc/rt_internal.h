@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstring>
 
 #include "rt_layout.h"
 #include "rt_slices.h"
@@ -14,6 +15,7 @@ namespace rt {
 constexpr int32_t kHostClusterAuto = 1;   // option "brute_cluster" is -1: only tiles of at least a pixel per resident lane are clustered
 constexpr int32_t kHostDirect = 4;        // ... and the enable of the in-place test (option "brute_direct"; rt_debug_last_direct)
 constexpr int32_t kHostQuad = 2;          // the shell's record has split faces (option "brute_quad"; rt_debug_last_launch)
+constexpr int32_t kHostLean = 8;          // every material emissive or diffuse (HostScene::diffuse_only) and option "brute_lean" not 0
 struct DevScene {
     // FAST traversal: BVH2 nodes holding both child boxes, 4 x float4 each:
     //   [0] = c0.min.x, c0.max.x, c0.min.y, c0.max.y
@@ -312,6 +314,26 @@ inline bool operator==(const KernelKey& a, const KernelKey& b) {
     return a.trav == b.trav && a.count == b.count && a.log == b.log && a.smem == b.smem && a.ovf == b.ovf &&
            a.resume == b.resume && a.step == b.step && a.wide == b.wide && a.brute == b.brute && a.ts == b.ts &&
            a.acc == b.acc;
+}
+// The lean form of the one-lane brute-force kernels (render_kernel's BRUTE_ bit kBruteLean; option "brute_lean"): a
+// loop without the glossy, glass, IBL and pilot code, for the launches whose frame cannot reach any of it.  A launch
+// is lean when the kernel launch_pick ends at is a one-lane brute-force product kernel of a one-shot frame (loop 1 or
+// 3: no teams, not instrumented, not logging, no accumulation) and brute_lean_frame holds:
+//   host_flags & kHostLean   every material's type is 0 or 1, and the option is not 0;
+//   env[4] is +0             the IBL term is then so x 0 x e4, which the lean loop writes as so x 0 -- equal bits for
+//                            +0 only, so -0, which sample_ibl_if takes for zero as well, keeps the general kernel;
+//   pass 0, pilot 0          one pass (a pilot launch's two passes carry state the lean loop does not restore);
+//   spp > 0, max_bounce >= 0 the loop's "no sample" and "no bounce" exits are not compiled in;
+//   fixed_point, sun_cache   on, their default: the lean loop has them on at compile time.
+constexpr int kBruteLean = 16;
+inline bool brute_lean_frame(int32_t host_flags, const FrameParams& fp) {
+    uint32_t e4;
+    std::memcpy(&e4, &fp.env[4], sizeof e4);
+    return (host_flags & kHostLean) != 0 && e4 == 0u && fp.pass == 0 && fp.pilot == 0 && fp.spp > 0 &&
+           fp.max_bounce >= 0 && fp.fixed_point != 0 && fp.sun_cache != 0;
+}
+inline bool brute_lean_kernel(const KernelKey& k, int team) {
+    return (k.brute & 3) != 0 && (k.brute & 3) != 2 && team <= 1 && k.trav == 0 && !k.count && !k.log && !k.acc && !k.resume;
 }
 // The engine of a pass over (sc, fp): REF, brute force, the plain, LDS-staged or overflow tree walk, the
 // resumable walk with its step and layout.  Pure: no device call.  brute is 0 or 1 and ts 1 here; the tile

@@ -64,6 +64,10 @@ constexpr int kBruteSliced = 4;
 // again), so that a launch without one -- the small tiles, where the threshold measured slower -- runs the code
 // it ran before.  The instrumented and logging kernels (COUNT, LOG) carry the threshold's code without the flag
 constexpr int kBruteRefill = 8;
+// ... and + kBruteLean (rt_internal.h: 16) for the one-shot launches brute_lean_frame admits -- every material emissive
+// or diffuse, no IBL term, one pass, fixed_point and sun_cache on -- whose loop holds none of the glossy, glass, IBL
+// and pilot code and reads no flag that the rule has fixed.  Every operation that shapes a bit stays: the frame is
+// the general kernel's
 template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, int ACC = 0>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
@@ -80,6 +84,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     static_assert(!SLICED || BRUTE == 1 || BRUTE == 3, "sample slices: the one-lane brute-force loops");
     constexpr bool kRefill = (BRUTE == 1 || BRUTE == 3) && ((BRUTE_ & kBruteRefill) != 0 || COUNT || LOG);
     static_assert(!(BRUTE_ & kBruteRefill) || BRUTE == 1 || BRUTE == 3, "refill threshold: the one-lane brute-force loops");
+    constexpr bool LEAN = (BRUTE_ & kBruteLean) != 0;
+    static_assert(!LEAN || ((BRUTE == 1 || BRUTE == 3) && TRAV == TRAV_FAST && !COUNT && !LOG && !ACC && RT_SHADE_ROWS),
+                  "lean: the one-lane one-shot product kernels");
     extern __shared__ __attribute__((aligned(16))) int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
@@ -180,7 +187,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
 
     int phase = FETCH;
     PixelQueue pq;
-    pq.per = (F.handout && F.pass != 2) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
+    pq.per = (F.handout && (LEAN || F.pass != 2)) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
     // FrameParams::refill = R rides in the hand-out's word, which the loop keeps anyway (a scalar register of
     // its own spills others that the shading reads)
     if constexpr (kRefill) pq.dry = F.refill > 1 ? (unsigned)min(F.refill, 64) << kQueueRefillShift : 0u;
@@ -284,7 +291,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 const bool whole = !SLICED || sl == kWholeJob;
                 bool ok = q < nloc;
                 if (ok) {
-                    p = (ACC == kAccListed || F.pass == 2) ? (int)F.pilot_order[q] : (int)q;
+                    if constexpr (LEAN) p = (int)q;   // (one pass: no cost order)
+                    else p = (ACC == kAccListed || F.pass == 2) ? (int)F.pilot_order[q] : (int)q;
                     const int krow = p / W;
                     const int col = p - krow * W;
                     const int64_t i64 = ((int64_t)F.row0 + (int64_t)krow * F.row_step) * W + col;
@@ -306,7 +314,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                     sun0 = -2;
                     phase = PRIMARY;
                     logme = LOG && i == F.log_pixel;
-                    if (F.pass == 2) {   // continue from the pilot state: camera hit cached, sample s next
+                    if (!LEAN && F.pass == 2) {   // continue from the pilot state: camera hit cached, sample s next
                         const float4 a = F.pilot_state[2 * (int64_t)p], b = F.pilot_state[2 * (int64_t)p + 1];
                         acc = rtm_v3(a.x, a.y, a.z);
                         kc = a.w;
@@ -369,7 +377,31 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             const bool cam = j == 0;
             const rtm_f3 Ro = cam ? C.position : Bo, Rd = cam ? cd : Bd;
             const float kh = cam ? kc : k;
-            if (j > maxB) {
+            if constexpr (LEAN) {
+                // max_bounce >= 0: j never passes it (the bounce at j == maxB ends the sample, below).  e4 is +0: the
+                // IBL term of a ray that left the scene is so x 0 -- (so x 0) x +0 keeps its bits, NaN and sign.  A
+                // surface is emissive (type 0) or diffuse: its row says which, and no other type's code is here
+                if (tri < 0) {
+                    so = rtm_mul(so, rtm_v3(0.0f, 0.0f, 0.0f));
+                } else {
+                    const float4 sh = trow[2 * tri], r1 = trow[2 * tri + 1];
+                    if ((int)sh.w == 0) {
+                        so = rtm_scale(so, r1.w);
+                    } else {
+                        const float4 f2 = tframe[3 * tri + 2];
+                        const rtm_f3 nn = xyz(f2);
+                        float invPdf = 0.0f;
+                        Bd = hemi_cosine(xyz(sh), tframe[3 * tri], tframe[3 * tri + 1], f2, &seed1, &seed0, &invPdf);
+                        const rtm_f3 brdf = rtm_scale(rtm_v3(r1.x, r1.y, r1.z), 1.0f / 3.14f);
+                        const rtm_f3 nd = dev_normalize(Rd);
+                        Bo = rtm_v3(fmaf(nd.x, kh, Ro.x), fmaf(nd.y, kh, Ro.y), fmaf(nd.z, kh, Ro.z));
+                        const float att = invPdf * rtm_fabs(rtm_dot(Bd, nn));
+                        so = rtm_scale(rtm_mul(so, brdf), att);
+                        phase = BOUNCE;
+                        done = false;
+                    }
+                }
+            } else if (j > maxB) {
                 // naiveGI's loop never entered (maxBounce < 0): the sample stays 1
             } else if (tri < 0) {
                 so = rtm_scale(rtm_mul(so, sample_ibl_if<COUNT>(S, C, Rd, e4, c)), e4);
@@ -416,17 +448,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                 // numbers, so the RNG state is unchanged and every later sample of the pixel is this
                 // sample again (same cached camera hit, same state): their colours are added in order,
                 // bit for bit the reference's sum (FrameParams::fixed_point).
-                if (TRAV == TRAV_FAST && F.fixed_point && j == 0 && !(LOG && logme)) {
+                if (TRAV == TRAV_FAST && (LEAN || F.fixed_point) && j == 0 && !(LOG && logme)) {
                     if (COUNT) c.samples += (unsigned long long)max(slimit() - s, 0);
                     for (; s < slimit(); ++s) acc = rtm_add(acc, so);
                 }
                 if (s >= slimit()) {
                     phase = FETCH;
                     if (team_leader) store_pixel(out, p, acc, slimit());
-                    if (F.pass == 1) save_pilot();
+                    if (!LEAN && F.pass == 1) save_pilot();
                     if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                     if constexpr (SLICED) { if (lim < spp) save_slice(cd); }   // done early: its later slices find nothing to do
-                } else if (F.pass == 1 && s >= F.pilot) {
+                } else if (!LEAN && F.pass == 1 && s >= F.pilot) {
                     save_pilot();
                     phase = FETCH;
                 } else if (SLICED && s >= lim) {
@@ -459,7 +491,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             tri = tc; j = 0;
             so = rtm_v3(1, 1, 1);
             phase = PREP;
-            if (spp <= 0) {   // reference: output = 0/0 -> NaN -> clamp gives 1
+            if (!LEAN && spp <= 0) {   // reference: output = 0/0 -> NaN -> clamp gives 1
                 if (team_leader) store_pixel(out, p, acc, spp);
                 phase = FETCH;
             }
@@ -472,12 +504,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         int sun_hit = -2;   // the shadow ray's hit for the sun term below (-1 = miss; -2 = no sun term now)
         // the first bounce leaves from the cached camera hit in every sample of the pixel, so its shadow
         // ray towards the sun is the same ray each time: traced once per pixel (FrameParams::fixed_point)
-        const bool sun_first = TRAV == TRAV_FAST && F.sun_cache && j == 0 && !(LOG && logme);
+        const bool sun_first = TRAV == TRAV_FAST && (LEAN || F.sun_cache) && j == 0 && !(LOG && logme);
         if (phase == BOUNCE) {
             if (h.tri >= 0) {
                 tri = h.tri; k = h.k;
-                const Mat bm = ROWS ? row_mat(trow[2 * h.tri], trow[2 * h.tri + 1])
-                                    : load_mat(tmat, __float_as_int(tshade[h.tri].w));
+                // (LEAN: the row's type word alone, and the emitter's power word where the type says emitter)
+                const Mat bm = LEAN ? Mat{(int)trow[2 * h.tri].w, rtm_v3(0, 0, 0), 0.0f}
+                               : ROWS ? row_mat(trow[2 * h.tri], trow[2 * h.tri + 1])
+                                      : load_mat(tmat, __float_as_int(tshade[h.tri].w));
                 if (bm.type != 0) {
                     if (j == maxB) {
                         so = rtm_v3(0, 0, 0);
@@ -487,7 +521,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                         phase = PREP;
                     }
                 } else {
-                    so = rtm_scale(so, bm.rough);
+                    so = rtm_scale(so, LEAN ? trow[2 * h.tri + 1].w : bm.rough);
                     finish = true;
                 }
             } else if (TRAV == TRAV_FAST && F.sun_skip) {
@@ -502,18 +536,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             if (sun_first) sun0 = h.tri;
         }
         if (sun_hit != -2) {  // SUN (Raytracing.cl:115-137)
-            rtm_f3 sunLight = rtm_v3(0, 0, 0);
             if (COUNT) c.sun++;
-            const Mat cm = ROWS ? row_mat(trow[2 * tri], trow[2 * tri + 1])
-                                : load_mat(tmat, __float_as_int(tshade[tri].w));
-            if (sun_hit < 0 && cm.type != 3) sunLight = rtm_v3(e3, e3, e3);
-            if (sun_hit >= 0) {
-                const Mat sm = ROWS ? row_mat(trow[2 * sun_hit], trow[2 * sun_hit + 1])
-                                    : load_mat(tmat, __float_as_int(tshade[sun_hit].w));
-                if (sm.type == 3) sunLight = rtm_scale(sm.color, e3);
+            if constexpr (LEAN) {
+                // neither the surface the bounce left nor an occluder is glass: the sun's light or none, and no row
+                // is read.  The IBL term is 0 x e4 = +0; its add stays, since e3 may be -0
+                const float l = (sun_hit < 0 ? e3 : 0.0f) + 0.0f;
+                so = rtm_mul(so, rtm_v3(l, l, l));
+            } else {
+                rtm_f3 sunLight = rtm_v3(0, 0, 0);
+                const Mat cm = ROWS ? row_mat(trow[2 * tri], trow[2 * tri + 1])
+                                    : load_mat(tmat, __float_as_int(tshade[tri].w));
+                if (sun_hit < 0 && cm.type != 3) sunLight = rtm_v3(e3, e3, e3);
+                if (sun_hit >= 0) {
+                    const Mat sm = ROWS ? row_mat(trow[2 * sun_hit], trow[2 * sun_hit + 1])
+                                        : load_mat(tmat, __float_as_int(tshade[sun_hit].w));
+                    if (sm.type == 3) sunLight = rtm_scale(sm.color, e3);
+                }
+                const rtm_f3 envLight = rtm_scale(sample_ibl_if<COUNT>(S, C, Bd, e4, c), e4);
+                so = rtm_mul(so, rtm_add(sunLight, envLight));
             }
-            const rtm_f3 envLight = rtm_scale(sample_ibl_if<COUNT>(S, C, Bd, e4, c), e4);
-            so = rtm_mul(so, rtm_add(sunLight, envLight));
             finish = true;
         }
         if (finish) {
@@ -523,10 +564,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             ++s;
             if (s >= slimit()) {
                 if (team_leader) store_pixel(out, p, acc, slimit());
-                if (F.pass == 1) save_pilot();
+                if (!LEAN && F.pass == 1) save_pilot();
                 if constexpr (ACC) { if (team_leader) save_state(F.pilot_state, p, acc, kc, seed0, seed1, tc, s); }
                 phase = FETCH;   // (SLICED: s goes up by one here, so this is the pixel's last slice: lim == spp)
-            } else if (F.pass == 1 && s >= F.pilot) {
+            } else if (!LEAN && F.pass == 1 && s >= F.pilot) {
                 save_pilot();
                 phase = FETCH;
             } else if (SLICED && s >= lim) {
@@ -1154,6 +1195,16 @@ void engine_rows(std::vector<KernelRow>& t) {
         t.push_back(render_row<TRAV_FAST, COUNT, false, false, false, 1 | kBruteRefill>());
     }
 }
+// ... and, last, the lean forms of the one-lane brute-force product kernels (one-shot frames only)
+template <int LOOP>
+void lean_rows(std::vector<KernelRow>& t) {
+    if constexpr (RT_SHADE_ROWS && !kTuAcc) {
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteLean>());
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteLean>());
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteRefill | kBruteLean>());
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteRefill | kBruteLean>());
+    }
+}
 
 // ---- test hooks (rt_debug.h): device evaluation of the numerics contract and of
 // single rays through either traversal ----
@@ -1373,6 +1424,8 @@ const void* kernel_fn(const KernelKey& k) {
         head_rows<false>(t);
 #endif
         engine_rows<false>(t);
+        lean_rows<3>(t);
+        lean_rows<1>(t);
         return t;
     }();
     for (const KernelRow& r : table)
@@ -1433,6 +1486,9 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     k.ts = f.walk_team;
     if (brute && f.team > 1) k.brute = 2;
     else if (brute) k.brute |= (bslices ? kBruteSliced : 0) | (product && f.refill > 1 ? kBruteRefill : 0);
+    // ... and so is the lean loop of an all-diffuse one-shot frame (rt_internal.h: the rule; one-shot kernels only, so
+    // rt_accum.hip's and rt_adaptive.hip's translation units hold none)
+    if (RT_SHADE_ROWS && !kTuAcc && brute_lean_kernel(k, f.team) && brute_lean_frame(sc.host_flags, f)) k.brute |= kBruteLean;
     if (brute && f.team <= 1) lds = brute_lds_bytes(sc, block, false);
     const void* fn = kernel_fn(k);
     // the grid stays within what the device keeps resident (not that the slices' hand-off needs it: a job is only

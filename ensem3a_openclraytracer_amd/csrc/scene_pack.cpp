@@ -983,6 +983,13 @@ bool shell_direct(HostScene& hs, int direct) {
     return direct != 0;
 }
 
+bool materials_diffuse_only(const float* mat, int64_t nmat6) {
+    // (int)t is 0 or 1 exactly for -1 < t < 2; a NaN type fails both comparisons
+    for (int64_t m = 0; m < nmat6 / 6; ++m)
+        if (!(mat[6 * m] > -1.0f && mat[6 * m] < 2.0f)) return false;
+    return true;
+}
+
 void pack_checked(HostScene& hs, const float* bvh9, int64_t nb, int64_t ntri, int layout, int brute_max, int cluster,
                   int shell, int quad, std::string& why) {
     hs.fast_ok = (ntri > 0) ? pack_fast(hs, bvh9, nb, ntri, layout, brute_max, cluster, shell, quad, why) : true;
@@ -1056,6 +1063,7 @@ int scene_prepare_(HostScene& hs, const float* vp, int64_t nvp, const float* vn,
         for (int k = 1; k < 4; ++k) hs.colors_finite = hs.colors_finite && std::isfinite(mat[6 * m + k]);
         hs.has_glass = hs.has_glass || (int)mat[6 * m] == 3;
     }
+    hs.diffuse_only = materials_diffuse_only(mat, nmat);
     if (bvh9) hs.bvh9.assign(bvh9, bvh9 + nbvh);
     hs.tri_geo.assign((size_t)T * 12, 0.0f);
     hs.tri_shade.assign((size_t)T * 4, 0.0f);

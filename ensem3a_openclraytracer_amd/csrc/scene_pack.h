@@ -51,7 +51,12 @@ struct HostScene {
     bool fast_ok = false;
     bool colors_finite = true;     // every material colour finite (FrameParams::sun_skip)
     bool has_glass = false;        // some material has type 3 (FrameParams::sun_any)
+    bool diffuse_only = true;      // every material has type 0 or 1 (materials_diffuse_only; the lean brute-force kernels)
 };
+
+// The census behind HostScene::diffuse_only: every one of the nmat6 / 6 material rows (6 floats each, the type first)
+// has type 0 (emissive) or 1 (diffuse) as the kernels read it, (int)type.  True for an empty table.
+bool materials_diffuse_only(const float* mat, int64_t nmat6);
 
 
 // Validate and pack (KernelLauncher.py:38-72's buffers, FileManager.py:276-282's faceData,

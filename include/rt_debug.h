@@ -229,7 +229,8 @@ int rt_debug_last_slices(void);
 /* The process's last render launch, as its kernel got it.  out[0..10] = the kernel's key: traversal (0 FAST,
  * 1 REF), count (instrumented), log, smem (scene staged in LDS), ovf (stack overflow buffer), resume (the
  * resumable tree walk), step (1 item steps, 0 rounds), wide (0 BVH2, 1 the 4-wide layout, 2 with origin-folded
- * dequantisation), brute (0 none, 1 lock-step, 2 teams, 3 clustered, + 4 sample slices, + 8 refill threshold),
+ * dequantisation), brute (0 none, 1 lock-step, 2 teams, 3 clustered, + 4 sample slices, + 8 refill threshold, + 16
+ * the lean form: rt_debug_brute_lean),
  * ts (lanes per pixel of the tree walk), acc (0 one-shot, 1 an add, 2 a listed add); out[11..14] = the brute-force
  * team size, the walk's team size, the slice word (rt_debug_last_slices) and R (rt_debug_last_refill) of its
  * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block; out[17] = 1 when the kernel
@@ -248,6 +249,19 @@ int rt_debug_brute_refill(int64_t nloc, int64_t lanes, int option, int32_t* out)
  * counters of the last instrumented launch (rt_count_work*): the render-loop iterations, per wave, that ran the
  * hand-out block, and the lanes that asked for a job in them (out[1] is counts[15] of rt_count_work_detail). */
 int rt_debug_last_refill(int64_t out[3]);
+
+/* No device call: the rule for the lean form of the one-lane brute-force kernels (option "brute_lean" = frame[6]: -1
+ * auto, 0 off, 1 auto), a loop without the glossy, glass, IBL and pilot code for the frames that reach none of it.
+ * materialData: n_mat floats, 6 per material, the type first; env: envData; frame = spp, maxBounce, the launch's pass
+ * (0: one pass) and pilot samples, options "fixed_point" and "sun_cache", the option; kernel = what the launch would
+ * otherwise run: the brute-force loop (0 none, 1 lock-step, 2 teams, 3 clustered), lanes per pixel, instrumented,
+ * logging, accumulation (0 one-shot, 1 an add, 2 a listed add), traversal (0 FAST, 1 REF).  out[0] = 1 when every
+ * material's type is 0 or 1 as the kernels read it (an empty table: 1), out[1] = 1 when the launch runs the lean
+ * kernel: out[0], the option not 0, a one-lane brute-force product kernel of a one-shot FAST frame, env[4] = +0 (not
+ * -0), one pass without a pilot, spp > 0, maxBounce >= 0, fixed_point and sun_cache on.  rt_debug_last_launch reports
+ * such a launch with 16 added to its key's brute. */
+int rt_debug_brute_lean(const float* materialData, int64_t n_mat, const float env[5], const int32_t frame[7],
+                        const int32_t kernel[6], int32_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,9 @@ where the spill code sits.
         every loop (backward branch) of that kernel's ISA with its scratch accesses, SGPR-spill lane
         moves (v_readlane / v_writelane), global loads and LDS operations: a traversal loop should show
         no scratch access
+    python tools/kernel_resources.py --census OBJ MANGLED-NAME-PART
+        that kernel's instructions by class (VALU, SALU, LDS, vector and scalar memory, branches, v_readlane /
+        v_writelane, waits), over its whole text and over its longest loop, as one JSON line
 """
 import os
 import re
@@ -46,9 +49,59 @@ def loops(obj, pat):
                   f"{cnt('v_readlane', 'v_writelane')} global_load {cnt('global_load')} lds {cnt('ds_read', 'ds_write')}")
 
 
+def census(obj, pat):
+    """Instructions by class in the kernel's text and in its longest loop (the render loop), as one JSON line."""
+    import json
+    with tempfile.TemporaryDirectory() as td:
+        co = code_object(obj, td)
+        isa = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--symbolize-operands", co], capture_output=True,
+                             text=True).stdout.split("\n")
+    starts = [i for i, l in enumerate(isa) if re.match(r"^[0-9a-f]+ <_Z", l)] + [len(isa)]
+    body = next((isa[a:b] for a, b in zip(starts, starts[1:]) if pat in isa[a]), None)
+    if body is None:
+        raise SystemExit(f"no kernel matching {pat!r}")
+
+    def count(seg):
+        c = dict(instructions=0, valu=0, salu=0, lds=0, vmem=0, smem=0, branches=0, v_readlane=0, v_writelane=0, waitcnt=0)
+        for x in seg:
+            m = re.match(r"^\s+([a-z]\w+)", x)
+            if not m:
+                continue
+            op = m.group(1)
+            c["instructions"] += 1
+            c["v_readlane"] += op.startswith("v_readlane")
+            c["v_writelane"] += op.startswith("v_writelane")
+            if op.startswith("s_waitcnt"):
+                c["waitcnt"] += 1
+            elif op.startswith(("s_cbranch", "s_branch")):
+                c["branches"] += 1
+            elif op.startswith(("s_load", "s_buffer_load")):
+                c["smem"] += 1
+            elif op.startswith("s_"):
+                c["salu"] += 1
+            elif op.startswith("ds_"):
+                c["lds"] += 1
+            elif op.startswith(("global_", "flat_", "buffer_", "scratch_")):
+                c["vmem"] += 1
+            elif op.startswith("v_"):
+                c["valu"] += 1
+        return c
+
+    labels = {m.group(1): k for k, x in enumerate(body) if (m := re.match(r"^[0-9a-f]+ <(L\d+)>:", x))}
+    best = (0, 0)
+    for k, x in enumerate(body):
+        m = re.search(r"s_(?:cbranch_\w+|branch) (L\d+)", x)
+        if m and labels.get(m.group(1), k) < k and k - labels[m.group(1)] > best[1] - best[0]:
+            best = (labels[m.group(1)], k)
+    print(json.dumps({"kernel": body[0].split("<")[1].split(">")[0], "text": count(body),
+                      "longest_loop": count(body[best[0]:best[1] + 1])}))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--loops":
         return loops(sys.argv[2], sys.argv[3])
+    if len(sys.argv) > 1 and sys.argv[1] == "--census":
+        return census(sys.argv[2], sys.argv[3])
     obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(__file__), "..", "build", "native",
                                                               "rt_kernels.o")
     filt = sys.argv[2] if len(sys.argv) > 2 else "render"
