@@ -390,6 +390,107 @@ class KernelLauncher(object):
         material = torch.where(hit, table[tri.clamp(min=0).long()] if len(table) else tri, torch.full_like(tri, -1))
         return {"k": out[:, 0], "tri": tri, "u": out[:, 2], "v": out[:, 3], "hit": hit, "material": material}
 
+    def upload_env(self, h_IBL) -> None:
+        """Upload the environment map alone (what ``launch_Raytracing`` does with ``h_IBL``): ``radiance`` needs a
+        scene and an environment, and no frame."""
+        self._upload_env(h_IBL)
+
+    def camera_rays(self, cam, npix) -> tuple:
+        """The rays ``launch_Raytracing`` gives the ``npix`` pixels of ``cam``'s frame (rt_camera_rays of rt_api.h):
+        ``(origins [n, 3], directions [n, 3], seeds uint32 [n, 2])`` -- ``radiance`` of them is that frame."""
+        cam = _native.f32(cam).reshape(-1)
+        if cam.size < 10:
+            raise ValueError("cam needs 10 floats")
+        rays = self._ctx.camera_rays(cam[:10], int(npix))
+        return rays[:, 3:6].copy(), rays[:, 0:3].copy(), rays[:, 6:8].copy().view(np.uint32)
+
+    def radiance(self, origins, directions, spp, max_bounce, env, seeds=None, state=None) -> dict:
+        """Path-trace rays of the caller's own (rt_radiance of rt_api.h): ``spp`` samples of the frame's integrator
+        along each ray, under the launcher's traversal, with ``env`` and ``max_bounce`` as ``launch_Raytracing``
+        takes ``h_envData`` and ``maxBounce``.  ``origins`` and ``directions`` are ``[n, 3]`` (directions are used
+        as given, not normalised); ``seeds`` is uint32 ``[n, 2]``, the RNG state each ray starts from (None:
+        ``(ray index, 0)``, the decorrelation a frame gives its pixels).  The camera rays of a frame with that
+        frame's seeds (``camera_rays``) give that frame, bit for bit.
+
+        Returns ``rgb`` (``sum / float32(n)``, not clamped: a baker keeps values above 1), ``sum``, ``n`` (samples
+        done), ``k``, ``tri``, ``hit`` (the first hit, as ``trace_rays`` reports it) and ``state``.  Passing the
+        returned ``state`` back as ``state`` adds ``spp`` more samples to every ray -- after calls of ``a`` and
+        ``b`` samples the result is that of one call of ``a + b`` -- and ``seeds`` is then ignored; keeping a ray's
+        total at or below ``2**24`` samples is the caller's job.
+
+        numpy arrays go through the blocking host form, split over the launcher's devices.  Objects with
+        ``data_ptr()`` (torch tensors on the launcher's first device) go through the device form on torch's current
+        stream: nothing is copied to the host and the call does not wait; the results are tensors on that device
+        (``state`` an int32 ``[n, 8]`` tensor of the records' words, updated in place when passed back)."""
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be >= 1")
+        e = _native.f32(env).reshape(-1)
+        if e.size < 5:
+            raise ValueError("env needs 5 floats")
+        if hasattr(origins, "data_ptr") or hasattr(directions, "data_ptr"):
+            return self._radiance_torch(origins, directions, spp, int(max_bounce), e[:5], seeds, state)
+        o = np.asarray(origins, dtype=np.float32)
+        d = np.asarray(directions, dtype=np.float32)
+        for name, a in (("origins", o), ("directions", d)):
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name} must be [n, 3], got {list(a.shape)}")
+        rays = _native.pack_radiance_rays(o, d, seeds)   # (counts that differ, the seeds' shape and type)
+        if state is not None:
+            if not isinstance(state, np.ndarray) or state.dtype != _native.RADIANCE_STATE_DTYPE:
+                raise TypeError("state must be the 'state' array an earlier call returned")
+            if state.shape != (len(rays),):
+                raise ValueError(f"state holds {state.size} records, needs {len(rays)}")
+            state = np.ascontiguousarray(state)
+        st = self._ctx.radiance(rays, e[:5], spp, int(max_bounce), state=state)
+        n = st["n"].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rgb = st["sum"] / n.astype(np.float32)[:, None]
+        return {"rgb": rgb, "sum": st["sum"].copy(), "n": n, "k": st["k"].copy(), "tri": st["tri"].copy(),
+                "hit": st["tri"] >= 0, "state": st}
+
+    def _radiance_torch(self, origins, directions, spp, max_bounce, env, seeds, state) -> dict:
+        import torch
+        dev = origins.device if hasattr(origins, "data_ptr") else directions.device
+        o = torch.as_tensor(origins, dtype=torch.float32, device=dev)
+        d = torch.as_tensor(directions, dtype=torch.float32, device=dev)
+        for name, a in (("origins", o), ("directions", d)):
+            if a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"{name} must be [n, 3], got {list(a.shape)}")
+        if o.shape[0] != d.shape[0]:
+            raise ValueError(f"{o.shape[0]} origins but {d.shape[0]} directions")
+        n = o.shape[0]
+        rays = torch.zeros((n, _native.RAY_FLOATS), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = d
+        rays[:, 3:6] = o
+        words = rays.view(torch.int32)
+        if seeds is None:
+            words[:, 6] = torch.arange(n, dtype=torch.int32, device=dev)
+        else:
+            sd = torch.as_tensor(seeds, device=dev)
+            if sd.dtype.is_floating_point or sd.dtype == torch.bool:
+                raise TypeError(f"seeds must be integers, got {sd.dtype}")
+            if tuple(sd.shape) != (n, 2):
+                raise ValueError(f"seeds must be [{n}, 2], got {list(sd.shape)}")
+            words[:, 6:8] = sd.to(torch.int64).to(torch.int32)   # (the low 32 bits: uint32 seeds keep theirs)
+        flags = 0
+        if state is not None:
+            if not hasattr(state, "data_ptr") or state.dtype != torch.int32 or not state.is_contiguous():
+                raise TypeError("state must be the contiguous int32 'state' tensor an earlier call returned")
+            if tuple(state.shape) != (n, 8) or state.device != rays.device:
+                raise ValueError(f"state must be [{n}, 8] on {rays.device}, got {list(state.shape)} on {state.device}")
+            flags = _native.RT_RADIANCE_RESUME
+        else:
+            state = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        if n:
+            self._ctx.radiance_device(0, rays.data_ptr(), n, env, spp, max_bounce, flags, state.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+        total = state[:, 0:3].view(torch.float32)
+        count = state[:, 7]
+        tri = state[:, 6]
+        return {"rgb": total / count.to(torch.float32)[:, None], "sum": total, "n": count,
+                "k": state[:, 3].view(torch.float32), "tri": tri, "hit": tri >= 0, "state": state}
+
     def launch_ImgProcessing(self, h_src, h_out, SIZE):
         """Gamma 2.2 of ``ImgProcessing.cl``: ``h_out[k] = min(h_src[k], 1) ** 2.2`` for ``k < 3*SIZE*SIZE``."""
         src = _native.f32(h_src).reshape(-1)

@@ -37,6 +37,7 @@ EXPORTED = (
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
     "rt_trace", "rt_trace_device",
+    "rt_radiance", "rt_radiance_device", "rt_camera_rays", "rt_camera_rays_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_trace_clustered", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
@@ -88,6 +89,37 @@ def pack_rays(origins, directions, tmax=None) -> np.ndarray:
     rays[:, 0:3] = d
     rays[:, 3:6] = o
     rays[:, 6] = QUERY_HORIZON if tmax is None else np.asarray(tmax, dtype=np.float32)
+    return rays
+
+
+# Radiance queries (rt_radiance*, rt_api.h): rt_radiance_state, and a ray's eight words dir.xyz, origin.xyz, seed0,
+# seed1 (the seeds' uint bits where rt_trace has tmax and reserved)
+RADIANCE_STATE_DTYPE = np.dtype([("sum", np.float32, (3,)), ("k", np.float32), ("seed0", np.uint32),
+                                 ("seed1", np.uint32), ("tri", np.int32), ("n", np.int32)])
+RT_RADIANCE_RESUME = 1
+RT_ACCUM_MAX_SAMPLES = 1 << 24
+
+
+def pack_radiance_rays(origins, directions, seeds=None) -> np.ndarray:
+    """float32 ``[n, 8]`` rays of rt_radiance from ``[n, 3]`` origins and directions: ``dir, origin``, then the bits
+    of ``seeds`` (uint32 ``[n, 2]``; None: ``(ray index, 0)``, the decorrelation a frame gives its pixels)."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError(f"{len(o)} origins but {len(d)} directions")
+    rays = np.zeros((len(o), RAY_FLOATS), np.float32)
+    rays[:, 0:3] = d
+    rays[:, 3:6] = o
+    words = rays.view(np.uint32)
+    if seeds is None:
+        words[:, 6] = np.arange(len(o), dtype=np.uint32)
+    else:
+        sd = np.asarray(seeds)
+        if sd.dtype.kind not in "iu":
+            raise TypeError(f"seeds must be integers, got {sd.dtype}")
+        if sd.shape != (len(o), 2):
+            raise ValueError(f"seeds must be [{len(o)}, 2], got {list(sd.shape)}")
+        words[:, 6:8] = sd.astype(np.uint32)
     return rays
 
 
@@ -176,6 +208,10 @@ def lib():
             "rt_accum_denoise": (_i32, [_c_p, ctypes.POINTER(DenoiseParams), _c_p]),
             "rt_trace": (_i32, [_c_p, _c_p, _i64, _i32, _c_p]),
             "rt_trace_device": (_i32, [_c_p, _i32, _c_p, _i64, _i32, _c_p, _c_p]),
+            "rt_radiance": (_i32, [_c_p, _c_p, _i64, _c_p, _i32, _i32, _i32, _c_p]),
+            "rt_radiance_device": (_i32, [_c_p, _i32, _c_p, _i64, _c_p, _i32, _i32, _i32, _c_p, _c_p]),
+            "rt_camera_rays": (_i32, [_c_p, _c_p, _i64, _i64, _i64, _c_p]),
+            "rt_camera_rays_device": (_i32, [_c_p, _i32, _c_p, _i64, _i64, _i64, _c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -536,6 +572,60 @@ class Context:
         self._check(lib().rt_trace_device(self.handle, int(device_index), _c_p(int(rays_ptr)) if rays_ptr else None,
                                           int(n), int(mode), _c_p(int(out_ptr)) if out_ptr else None,
                                           self._stream(stream_ptr)))
+
+    # -- radiance queries (rt_radiance / rt_radiance_device, rt_camera_rays*) --
+    def radiance(self, rays8, env, spp: int, max_bounce: int, state: np.ndarray = None) -> np.ndarray:
+        """rt_radiance: ``rays8`` float32 ``[n, 8]`` (``pack_radiance_rays``) -> a ``RADIANCE_STATE_DTYPE`` array
+        ``[n]``, blocking.  ``state`` (such an array, updated in place and returned) resumes its records."""
+        r = np.ascontiguousarray(rays8, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != RAY_FLOATS:
+            raise ValueError(f"rays must be [n, {RAY_FLOATS}] float32, got {list(r.shape)}")
+        n = len(r)
+        e = f32(env).reshape(-1)
+        if e.size < 5:
+            raise ValueError("env needs 5 floats")
+        flags = 0
+        if state is not None:
+            if not isinstance(state, np.ndarray) or state.dtype != RADIANCE_STATE_DTYPE or not state.flags.c_contiguous:
+                raise TypeError("state must be a C-contiguous RADIANCE_STATE_DTYPE numpy array")
+            if state.shape != (n,):
+                raise ValueError(f"state has shape {list(state.shape)}, needs [{n}]")
+            flags = RT_RADIANCE_RESUME
+        else:
+            state = np.zeros(n, RADIANCE_STATE_DTYPE)
+        self._check(lib().rt_radiance(self.handle, ptr(r) if n else None, n, ptr(e), int(spp), int(max_bounce), flags,
+                                      state.ctypes.data if n else None))
+        return state
+
+    def radiance_device(self, device_index: int, rays_ptr: int, n: int, env, spp: int, max_bounce: int, flags: int,
+                        state_ptr: int, stream_ptr: int = 0) -> None:
+        """rt_radiance_device: device arrays on slot ``device_index``, enqueued on the stream; never waits."""
+        e = f32(env).reshape(-1)
+        if e.size < 5:
+            raise ValueError("env needs 5 floats")
+        self._check(lib().rt_radiance_device(self.handle, int(device_index), _c_p(int(rays_ptr)) if rays_ptr else None,
+                                             int(n), ptr(e), int(spp), int(max_bounce), int(flags),
+                                             _c_p(int(state_ptr)) if state_ptr else None, self._stream(stream_ptr)))
+
+    def camera_rays(self, cam, npix: int, first: int = 0, count: int = None) -> np.ndarray:
+        """rt_camera_rays: float32 ``[count, 8]`` rays (with seeds) of pixels ``first .. first + count - 1``."""
+        c = f32(cam).reshape(-1)
+        if c.size < 10:
+            raise ValueError("cam needs 10 floats")
+        count = int(npix) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), RAY_FLOATS), np.float32)
+        self._check(lib().rt_camera_rays(self.handle, ptr(c), int(npix), int(first), count,
+                                         out.ctypes.data if count > 0 else None))
+        return out
+
+    def camera_rays_device(self, device_index: int, cam, npix: int, first: int, count: int, rays_ptr: int,
+                           stream_ptr: int = 0) -> None:
+        c = f32(cam).reshape(-1)
+        if c.size < 10:
+            raise ValueError("cam needs 10 floats")
+        self._check(lib().rt_camera_rays_device(self.handle, int(device_index), ptr(c), int(npix), int(first),
+                                                int(count), _c_p(int(rays_ptr)) if rays_ptr else None,
+                                                self._stream(stream_ptr)))
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

@@ -98,6 +98,9 @@ struct Device {
     // Ray queries (rt_trace*): the hand-out counter of the persistent kernels and, for the host form, this slot's
     // rays and results -- buffers of their own, allocated on first use
     DevBuf q_counter, q_rays, q_out;
+    // Radiance queries (rt_radiance*, rt_camera_rays*): the launch's work block (hand-out counter + launch constants)
+    // and, for the host form, this slot's records (its rays go through q_rays) -- allocated on first use
+    DevBuf rad_work, rad_state;
     char* host_stage = nullptr;   // pinned staging for rt_render / rt_render_rgb8
     int* host_pick = nullptr;     // pinned: a two-pass launch's pass-2 pick, read back (rt::RenderPending)
     size_t host_stage_bytes = 0;
@@ -164,6 +167,7 @@ struct rt_ctx {
     int denoise_lds = -1;    // the filter's pass at step 1 stages its tile in LDS (0 off, 1 on, -1 auto: kDenoiseLds)
     int query_engine = 0;    // ray queries: 0 auto, 1 the plain form, 2 the persistent form (option "query_engine")
     int query_grid = 0;      // ... at most this many blocks of the persistent form (0 auto; option "query_grid")
+    int radiance_grid = 0;   // radiance queries: at most this many blocks (0 auto; option "radiance_grid")
     bool accum_host = false;   // the open accumulation is rt_accum_begin's: every slot holds its rows of one frame
     // host wall times of the last calls (rt_debug_timings), ms: rt_set_scene's validation + packing and its
     // uploads (+ the per-triangle frame kernel), rt_set_env (upload + texel-sum kernel), rt_render's
@@ -512,6 +516,7 @@ const std::vector<Option>& options() {
         {"denoise_lds", &rt_ctx::denoise_lds, range(-1, 1), "denoise_lds must be -1 (auto), 0 or 1", none},
         {"query_engine", &rt_ctx::query_engine, range(0, 2), "query_engine must be 0 (auto), 1 (plain) or 2 (persistent)", none},
         {"query_grid", &rt_ctx::query_grid, range(0, 1 << 20), "query_grid must be 0 (auto) or a block count", none},
+        {"radiance_grid", &rt_ctx::radiance_grid, range(0, 1 << 20), "radiance_grid must be 0 (auto) or a block count", none},
         {"wdq", &rt_ctx::wdq, range(0, 1), "wdq must be 0 or 1", none},
         {"handout", &rt_ctx::handout, range(-1, 1), "handout must be -1 (auto), 0 or 1", none},
         {"spec", &rt_ctx::spec, one_of({-1, 0, 2, 4, 8}), "spec must be -1 (auto), 0 (off), 2, 4 or 8", none},
@@ -1729,6 +1734,145 @@ int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out) {
         HIP_OR_RET(ctx, hipSetDevice(d.id));
         HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
     }
+    return RT_OK;
+}
+
+static_assert(sizeof(rt_radiance_state) == 32, "rt_radiance_state is the accumulation's state record: two float4");
+namespace {
+// the argument and state checks the two radiance entry points share (n > 0 past them)
+int radiance_check(rt_ctx* ctx, const void* rays, int64_t n, const float* env, int spp, int max_bounce, int flags,
+                   const void* state) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (n < 0 || n >= ((int64_t)1 << 31)) return set_err(ctx, RT_ERR_ARG, "ray count %lld out of range", (long long)n);
+    if (spp < 1 || spp > RT_ACCUM_MAX_SAMPLES) return set_err(ctx, RT_ERR_ARG, "spp %d outside 1..%d", spp, RT_ACCUM_MAX_SAMPLES);
+    if (flags & ~RT_RADIANCE_RESUME) return set_err(ctx, RT_ERR_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    if (max_bounce > 4096) return set_err(ctx, RT_ERR_ARG, "maxBounce %d > 4096", max_bounce);
+    if (!env) return set_err(ctx, RT_ERR_ARG, "env must not be NULL");
+    if (n > 0 && (!rays || !state)) return set_err(ctx, RT_ERR_ARG, "rays / state must not be NULL");
+    if (!ctx->have_scene) return set_err(ctx, RT_ERR_STATE, "rt_set_scene has not been called");
+    if (!ctx->have_env) return set_err(ctx, RT_ERR_STATE, "rt_set_env has not been called");
+    if (ctx->traversal == RT_TRAVERSAL_FAST && !ctx->hs.fast_ok)
+        return set_err(ctx, RT_ERR_STATE, "FAST traversal unavailable for this scene");
+    return RT_OK;
+}
+
+// one slot's launch: ordered with the context's other launches, never waits
+int radiance_enqueue(rt_ctx* ctx, Device& d, const float* d_rays, int64_t n, const float env[5], int spp,
+                     int max_bounce, int flags, rt_radiance_state* d_state, hipStream_t s) {
+    const rt::DevScene sc = dev_scene(ctx, d);
+    if (!rt::radiance_fits(sc, ctx->traversal, ctx->block))
+        return set_err(ctx, RT_ERR_SCENE, "a traversal stack of %d entries per lane does not fit a block of 64 lanes",
+                       ctx->traversal == RT_TRAVERSAL_REF ? (int)sc.ref_stack : (int)sc.depth);
+    HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
+    rt::RadianceOptions q{};
+    std::memcpy(q.env, env, sizeof q.env);
+    q.spp = spp;
+    q.max_bounce = max_bounce;
+    // the render loop's exact shortcuts, under the conditions check_frame sets them
+    q.flags = (flags & RT_RADIANCE_RESUME ? 1 : 0) |
+              (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite ? 2 : 0) |
+              (ctx->fixed_point ? 4 : 0) | (ctx->fixed_point && ctx->sun_cache ? 8 : 0);
+    q.grid_cap = ctx->radiance_grid;
+    q.max_waves = ctx->max_waves;
+    q.block = ctx->block;
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_radiance(sc, ctx->traversal, (const float4*)d_rays, (float4*)d_state, n, q, d.rad_work.p, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int camera_rays_check(rt_ctx* ctx, const float* cam, int64_t npix, int64_t first, int64_t count, const void* rays) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!cam) return set_err(ctx, RT_ERR_ARG, "cam must not be NULL");
+    if (!(cam[6] >= 1.0f) || !(cam[6] < 2147483648.0f))
+        return set_err(ctx, RT_ERR_ARG, "cam[6] (row width) must be >= 1, got %g", (double)cam[6]);
+    if (npix <= 0 || npix > 0x7fffffff) return set_err(ctx, RT_ERR_ARG, "pixel count %lld out of range", (long long)npix);
+    if (first < 0 || count < 0 || first > npix || count > npix - first)
+        return set_err(ctx, RT_ERR_ARG, "pixels %lld .. +%lld outside the frame of %lld", (long long)first,
+                       (long long)count, (long long)npix);
+    if (count > 0 && !rays) return set_err(ctx, RT_ERR_ARG, "rays must not be NULL");
+    return RT_OK;
+}
+
+int camera_rays_enqueue(rt_ctx* ctx, Device& d, const float cam[10], int64_t npix, int64_t first, int64_t count,
+                        float* d_rays, hipStream_t s) {
+    HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_camera_rays(cam, npix, first, count, (float4*)d_rays, d.rad_work.p, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+}  // namespace
+
+int rt_radiance_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, const float env[5], int spp,
+                       int max_bounce, int flags, rt_radiance_state* d_state, void* stream) {
+    Device* dp = nullptr;
+    int st = radiance_check(ctx, d_rays, n, env, spp, max_bounce, flags, d_state);
+    if (!st) st = slot_of(ctx, device_index, &dp);
+    if (st) return st;
+    if (n == 0) return RT_OK;
+    const uintptr_t r0 = (uintptr_t)d_rays, o0 = (uintptr_t)d_state;
+    if ((r0 & 15) || (o0 & 15)) return set_err(ctx, RT_ERR_ARG, "d_rays and d_state must be 16-byte aligned");
+    if (r0 < o0 + (uintptr_t)n * sizeof(rt_radiance_state) && o0 < r0 + (uintptr_t)n * 32)
+        return set_err(ctx, RT_ERR_ARG, "d_rays and d_state must not overlap");
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    return radiance_enqueue(ctx, *dp, d_rays, n, env, spp, max_bounce, flags, d_state, (hipStream_t)stream);
+}
+
+int rt_radiance(rt_ctx* ctx, const float* rays, int64_t n, const float env[5], int spp, int max_bounce, int flags,
+                rt_radiance_state* state) {
+    const int st = radiance_check(ctx, rays, n, env, spp, max_bounce, flags, state);
+    if (st) return st;
+    if (n == 0) return RT_OK;
+    // contiguous chunks over the slots; every slot is enqueued before any is waited for
+    const int64_t nd = (int64_t)ctx->devs.size();
+    for (int64_t k = 0; k < nd; ++k) {
+        const int64_t b = n * k / nd, m = n * (k + 1) / nd - b;
+        if (m <= 0) continue;
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, grow(d, d.q_rays, (size_t)m * 32));
+        HIP_OR_RET(ctx, grow(d, d.rad_state, (size_t)m * sizeof(rt_radiance_state)));
+        HIP_OR_RET(ctx, hipMemcpyAsync(d.q_rays.p, rays + 8 * b, (size_t)m * 32, hipMemcpyHostToDevice, d.stream));
+        if (flags & RT_RADIANCE_RESUME)
+            HIP_OR_RET(ctx, hipMemcpyAsync(d.rad_state.p, state + b, (size_t)m * sizeof(rt_radiance_state),
+                                           hipMemcpyHostToDevice, d.stream));
+        const int qs = radiance_enqueue(ctx, d, (const float*)d.q_rays.p, m, env, spp, max_bounce, flags,
+                                        (rt_radiance_state*)d.rad_state.p, d.stream);
+        if (qs) return qs;
+        HIP_OR_RET(ctx, hipMemcpyAsync(state + b, d.rad_state.p, (size_t)m * sizeof(rt_radiance_state),
+                                       hipMemcpyDeviceToHost, d.stream));
+    }
+    for (auto& d : ctx->devs) {
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    }
+    return RT_OK;
+}
+
+int rt_camera_rays_device(rt_ctx* ctx, int device_index, const float cam[10], int64_t npix, int64_t first,
+                          int64_t count, float* d_rays, void* stream) {
+    Device* dp = nullptr;
+    int st = camera_rays_check(ctx, cam, npix, first, count, d_rays);
+    if (!st) st = slot_of(ctx, device_index, &dp);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    if ((uintptr_t)d_rays & 15) return set_err(ctx, RT_ERR_ARG, "d_rays must be 16-byte aligned");
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    return camera_rays_enqueue(ctx, *dp, cam, npix, first, count, d_rays, (hipStream_t)stream);
+}
+
+int rt_camera_rays(rt_ctx* ctx, const float cam[10], int64_t npix, int64_t first, int64_t count, float* rays) {
+    const int st = camera_rays_check(ctx, cam, npix, first, count, rays);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    Device& d = ctx->devs[0];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, grow(d, d.q_rays, (size_t)count * 32));
+    const int qs = camera_rays_enqueue(ctx, d, cam, npix, first, count, (float*)d.q_rays.p, d.stream);
+    if (qs) return qs;
+    HIP_OR_RET(ctx, hipMemcpyAsync(rays, d.q_rays.p, (size_t)count * 32, hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
     return RT_OK;
 }
 

@@ -358,6 +358,28 @@ struct QueryOptions {
 };
 hipError_t launch_query(const DevScene& sc, int traversal, int any, const float4* rays, float4* out, int64_t n,
                         const QueryOptions& q, unsigned int* counter, hipStream_t stream);
+// Radiance queries (rt_radiance*, rt_camera_rays*, rt_api.h; kernels in rt_radiance.hip's translation unit): n rays
+// (two float4 each: dir.xyz origin.x | origin.yz seed0 seed1) -> n state records (two float4 each: sum.xyz k | seed0
+// seed1 tri n, save_state's layout), spp samples of naiveGI each, enqueued on `stream`.  REF, brute force (the global
+// records) or trace_fast over the BVH2 nodes with the whole stack in LDS: radiance_fits says whether that stack fits a
+// block of 64 lanes.  work: radiance_work_bytes() of device scratch (the hand-out counter, zeroed by the launch, and
+// the launch constants, made by it).  launch_camera_rays writes rays first .. first + count - 1 of cam's frame of npix
+// pixels, with the seeds a render gives those pixels.
+constexpr size_t kRadConstOffset = 256;
+struct RadianceOptions {
+    float env[5];
+    int spp, max_bounce;
+    int flags;        // rt_radiance.hip: resume, sun_skip, fixed_point, sun_cache
+    int grid_cap;     // option "radiance_grid": at most this many blocks (0: the resident ones)
+    int max_waves;    // option "waves"
+    int block;
+};
+size_t radiance_work_bytes();
+bool radiance_fits(const DevScene& sc, int traversal, int block);
+hipError_t launch_radiance(const DevScene& sc, int traversal, const float4* rays, float4* state, int64_t n,
+                           const RadianceOptions& q, void* work, hipStream_t stream);
+hipError_t launch_camera_rays(const float cam[10], int64_t npix, int64_t first, int64_t count, float4* rays,
+                              void* work, hipStream_t stream);
 // test hooks
 // The process's last render launch (launch_pick) as its kernel got it: the refined key, FrameParams::team,
 // walk_team, slices and refill (0: every lane refilled at once), the grid and the dynamic LDS bytes

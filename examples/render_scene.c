@@ -15,7 +15,11 @@
  * gamma kernel (rt_gamma, ImgProcessing.cl), and writes OUT_PREFIX.f32 (float32 RGB),
  * OUT_PREFIX.rgb8 and OUT_PREFIX.gamma.f32.  With ADDS (1 <= ADDS <= spp) the frame is rendered
  * progressively instead: the spp samples in ADDS calls of rt_accum_add (and of rt_accum_add_rgb8 for the
- * 8-bit frame) on one accumulation each -- the files are the same bytes.  Exit status 0 on success. */
+ * 8-bit frame) on one accumulation each -- the files are the same bytes.  With the word "radiance" in place of
+ * ADDS the frame is also rendered through the radiance queries: rt_camera_rays writes the frame's rays and seeds,
+ * rt_radiance path-traces them in two calls (the second resumes the records), and clamp(sum / n) of every record
+ * must be rt_render's pixel, bit for bit -- what a host with a camera of its own would do with its own rays.
+ * Exit status 0 on success. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -60,10 +64,11 @@ static int take(reader* r, void* dst, long bytes) {
 
 int main(int argc, char** argv) {
     if (argc != 4 && argc != 5) {
-        fprintf(stderr, "usage: %s SCENE.obj PARAMS.bin OUT_PREFIX [ADDS]\n", argv[0]);
+        fprintf(stderr, "usage: %s SCENE.obj PARAMS.bin OUT_PREFIX [ADDS | radiance]\n", argv[0]);
         return 2;
     }
-    const int adds = argc == 5 ? atoi(argv[4]) : 0;   /* 0: one-shot rt_render */
+    const int radiance = argc == 5 && strcmp(argv[4], "radiance") == 0;
+    const int adds = argc == 5 && !radiance ? atoi(argv[4]) : 0;   /* 0: one-shot rt_render */
     int rc = 1;
     rt_obj* obj = NULL;
     rt_ctx* ctx = NULL;
@@ -72,6 +77,8 @@ int main(int argc, char** argv) {
     float *vp = NULL, *vn = NULL, *vuv = NULL, *mat = NULL, *bvh = NULL, *out = NULL, *gam = NULL;
     int32_t* face = NULL;
     uint8_t *ibl = NULL, *out8 = NULL;
+    float* rays = NULL;
+    rt_radiance_state* recs = NULL;
 
     long tlen = 0, plen = 0;
     text = (char*)read_file(argv[1], &tlen);
@@ -126,7 +133,7 @@ int main(int argc, char** argv) {
     gam = (float*)malloc(sizeof(float) * 3 * (size_t)npix);
     out8 = (uint8_t*)malloc(3 * (size_t)npix);
     if (!out || !gam || !out8) FAIL("out of memory");
-    if (argc == 5) {
+    if (argc == 5 && !radiance) {
         /* progressive: the frame after every add is a finished frame at the samples done so far (a viewer
          * would show each); the last one is the one-shot frame */
         if (adds < 1 || adds > spp) FAIL("ADDS must be in 1..spp");
@@ -148,6 +155,30 @@ int main(int argc, char** argv) {
         if (rt_render_rgb8(ctx, cam, env, npix, spp, max_bounce, 0, out8) != RT_OK)
             FAIL("rt_render_rgb8: %s", rt_last_error(ctx));
     }
+    if (radiance) {
+        /* the same frame from rays in memory: the camera's here, any rays of the host's own elsewhere */
+        if (spp < 1) FAIL("radiance needs spp >= 1");
+        rays = (float*)malloc(sizeof(float) * 8 * (size_t)npix);
+        recs = (rt_radiance_state*)malloc(sizeof(rt_radiance_state) * (size_t)npix);
+        if (!rays || !recs) FAIL("out of memory");
+        if (rt_camera_rays(ctx, cam, npix, 0, npix, rays) != RT_OK) FAIL("rt_camera_rays: %s", rt_last_error(ctx));
+        const int head = spp / 2;   /* two calls: the second continues the records of the first */
+        if (head > 0 && rt_radiance(ctx, rays, npix, env, head, max_bounce, 0, recs) != RT_OK)
+            FAIL("rt_radiance: %s", rt_last_error(ctx));
+        if (rt_radiance(ctx, rays, npix, env, spp - head, max_bounce, head > 0 ? RT_RADIANCE_RESUME : 0, recs) != RT_OK)
+            FAIL("rt_radiance: %s", rt_last_error(ctx));
+        for (int64_t p = 0; p < npix; ++p) {
+            if (recs[p].n != spp) FAIL("ray %lld holds %d samples", (long long)p, (int)recs[p].n);
+            for (int ch = 0; ch < 3; ++ch) {
+                const float v = recs[p].sum[ch] / (float)recs[p].n;
+                const float lo = v < 1.0f ? v : 1.0f;   /* fmin(v, 1): NaN goes to 1 (Raytracing.cl:211-220) */
+                const float px = lo > 0.0f ? lo : 0.0f;
+                if (memcmp(&px, &out[3 * p + ch], sizeof px) != 0)
+                    FAIL("radiance query differs from rt_render at pixel %lld", (long long)p);
+            }
+        }
+        printf("radiance queries of the camera rays: the same %d pixels\n", npix);
+    }
     if (rt_gamma(ctx, out, gam, 3 * (int64_t)npix) != RT_OK) FAIL("rt_gamma: %s", rt_last_error(ctx));
     /* a call the boundary must refuse, and say why */
     if (rt_set_option(ctx, "no_such_option", 1) == RT_OK) FAIL("an unknown option was accepted");
@@ -166,5 +197,6 @@ done:
     if (obj) rt_obj_free(obj);
     free(text); free(params); free(vp); free(vn); free(vuv); free(face); free(mat); free(bvh);
     free(ibl); free(out); free(gam); free(out8);
+    free(rays); free(recs);
     return rc;
 }

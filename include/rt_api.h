@@ -304,6 +304,54 @@ int rt_trace(rt_ctx* ctx, const float* rays, int64_t n, int mode, rt_hit* out);
 int rt_trace_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, int mode, rt_hit* d_out,
                     void* stream);
 
+/* Radiance queries: the frame's integrator (naiveGI under the sample loop, Raytracing.cl:46-151, 184-209) on the
+ * caller's own rays with the caller's own RNG seeds (no counterpart in the reference, which enters it through
+ * genCameraRay only).  Other cameras, depth of field, sub-pixel jitter, irradiance probes, light maps: the samples
+ * are a frame's samples.  The contract: the query of a frame's camera rays with that frame's seeds is that frame,
+ * bit for bit.
+ *
+ * A ray is eight 32-bit words (32 bytes): dir.xyz, origin.xyz -- rt_trace's first six -- then seed0, seed1 as uint
+ * bits where rt_trace has tmax and reserved.  The direction is used as given wherever the reference uses R_cam.dir
+ * unnormalised (rayTrace, BRDF_GGX's -R_cam.dir, the glass continuation) and normalised only where naiveGI does
+ * (R_bounce.o, Raytracing.cl:79).
+ * A result is the accumulation's 32-byte state record, rt_radiance_state: the sum of the samples, the first hit as
+ * rt_trace reports it under the context's "traversal" (tri = the row of faceData or -1, k = the distance or 1000.0f),
+ * the RNG words after the last sample and the sample count n.  The radiance is sum / (float)n; clamped to [0, 1] per
+ * channel it is rt_render's pixel at spp = n when the ray is genCameraRay(i, cam) with seeds (i % npix, i / npix).
+ *
+ * A fresh call traces the ray, starts from sum = 0, n = 0 and the ray's seeds, runs spp samples of naiveGI with
+ * max_bounce as rt_render takes it (negative: the bounce loop is never entered) and env as rt_render's, adds them in
+ * order and stores the record.  With RT_RADIANCE_RESUME the record is read instead: sum, k, tri, n and the seeds come
+ * from it, the ray's seed words are ignored and no first ray is traced; a stored tri outside [0, T) is a miss (and is
+ * stored back as -1).  Calls of a then b samples leave the record of one call of a + b, bit for bit.  Keeping a
+ * resumed ray's total at or below RT_ACCUM_MAX_SAMPLES is the caller's job: the host cannot see device records.
+ * Rays with NaN or infinite components are safe: they trace as rt_trace traces them and shade without faulting.
+ *
+ *   rt_radiance            host arrays, blocking: contiguous chunks over the device slots, every slot enqueued
+ *                          before any is waited for.
+ *   rt_radiance_device     DEVICE arrays on slot device_index, enqueued on the HIP stream `stream`; never waits.
+ *                          d_rays and d_state must be 16-byte aligned and must not overlap.
+ *   rt_camera_rays         the rays and seeds rt_render gives pixels first .. first + count - 1 of cam's frame of
+ *                          npix pixels, in the layout above (direction: genCameraRay's; origin: cam[0..2]); host
+ *                          array of 8 * count floats, blocking (device 0).  Needs no scene.
+ *   rt_camera_rays_device  the same into a 16-byte aligned device array, enqueued on `stream`.
+ * Ordering with the context's other work follows rt_trace; a query leaves an open accumulation untouched and valid.
+ * The engine: REF's DFS, brute force, or the BVH2 walk with its whole stack in LDS (the block shrinks to fit);
+ * RT_ERR_SCENE when that stack does not fit a block of 64 lanes.
+ * RT_ERR_STATE: no scene, no environment, or "traversal" is FAST and the scene has no FAST layout.  RT_ERR_ARG:
+ * n < 0, n >= 2^31, spp < 1, spp > RT_ACCUM_MAX_SAMPLES, max_bounce > 4096, unknown flag bits, NULL arrays with
+ * n > 0, misaligned or overlapping device arrays, a device index out of range; rt_camera_rays: a width below 1,
+ * npix outside 1 .. 2^31 - 1, pixels outside the frame.  n == 0 (count == 0) is RT_OK and launches nothing. */
+typedef struct { float sum[3]; float k; uint32_t seed0, seed1; int32_t tri; int32_t n; } rt_radiance_state; /* 32 bytes */
+enum { RT_RADIANCE_RESUME = 1 };
+int rt_radiance(rt_ctx* ctx, const float* rays, int64_t n, const float env[5], int spp, int max_bounce, int flags,
+                rt_radiance_state* state);
+int rt_radiance_device(rt_ctx* ctx, int device_index, const float* d_rays, int64_t n, const float env[5], int spp,
+                       int max_bounce, int flags, rt_radiance_state* d_state, void* stream);
+int rt_camera_rays(rt_ctx* ctx, const float cam[10], int64_t npix, int64_t first, int64_t count, float* rays);
+int rt_camera_rays_device(rt_ctx* ctx, int device_index, const float cam[10], int64_t npix, int64_t first,
+                          int64_t count, float* d_rays, void* stream);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),

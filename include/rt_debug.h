@@ -44,7 +44,8 @@
  *                  memory, -1 auto: 1) -- the same frame
  *   "query_engine" ray queries: 1 the plain form (one thread per ray, the whole stack in LDS), 2 the persistent
  *                  form (a resident grid over the ray stream), 0 auto -- the same closest hits bit for bit
- *   "query_grid"   ray queries, persistent form: at most this many blocks (0 auto: the resident ones) */
+ *   "query_grid"   ray queries, persistent form: at most this many blocks (0 auto: the resident ones)
+ *   "radiance_grid" radiance queries: at most this many blocks of the persistent grid (0 auto: the resident ones) */
 
 #ifdef __cplusplus
 extern "C" {
