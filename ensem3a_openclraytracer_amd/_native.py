@@ -948,7 +948,7 @@ def last_refill():
 
 
 LAUNCH_FIELDS = ("trav", "count", "log", "smem", "ovf", "resume", "step", "wide", "brute", "ts", "acc",
-                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near", "quad")
+                 "team", "walk_team", "slices", "refill", "grid", "lds", "shell", "near", "quad", "primary")
 BRUTE_SLICED = 4   # bits of the key's ``brute`` beside the loop (brute & 3: 1 lock-step, 2 teams, 3 clustered)
 BRUTE_REFILL = 8
 BRUTE_LEAN = 16    # the lean form of the one-lane kernels (option "brute_lean"; rt_debug_brute_lean has the rule)
@@ -957,7 +957,8 @@ BRUTE_LEAN = 16    # the lean form of the one-lane kernels (option "brute_lean";
 def last_launch() -> dict:
     """rt_debug_last_launch (include/rt_debug.h): the kernel key of the last render launch and the team sizes,
     slice word, refill threshold, grid and LDS bytes its kernel got, whether it walked a shell and whether that
-    shell's face tests had a non-zero floor (option "brute_near") and its record split walls (option "brute_quad"), by name
+    shell's face tests had a non-zero floor (option "brute_near") and its record split walls (option "brute_quad"), and
+    whether a pre-pass traced the launch's camera rays (option "brute_primary"), by name
     (``LAUNCH_FIELDS``)."""
     out = np.zeros(len(LAUNCH_FIELDS), np.int32)
     st = lib().rt_debug_last_launch(out.ctypes.data)

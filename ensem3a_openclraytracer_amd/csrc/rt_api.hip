@@ -142,6 +142,7 @@ struct rt_ctx {
     int brute_near = -1;     // ... whose face tests take the packer's floor (0 off, -1 or 1 auto; option "brute_near")
     int brute_direct = -1;   // ... and whose one queue step tests a lane's first record in place (0 off, -1 or 1 auto; option "brute_direct")
     int brute_lean = -1;     // the lean loop for all-diffuse one-shot frames (0 off, -1 or 1 auto; option "brute_lean"; rt_internal.h brute_lean_frame)
+    int brute_primary = -1;  // ... whose sliced launches trace their camera rays in a pre-pass (0 off, -1 or 1 auto; option "brute_primary"; rt_internal.h kBrutePrimary)
     int brute_quad = -1;     // ... and whose split walls queue one record (0 off, -1 or 1 auto; option "brute_quad")
     int resume_min = -1;
     int team = 0;  // brute-force lanes per pixel, 0 = auto
@@ -336,7 +337,8 @@ rt::DevScene dev_scene(const rt_ctx* ctx, const Device& d) {
     s.nsingle4 = s.ncslot - rt::kClusterSlots * s.ncluster;
     s.host_flags = (ctx->brute_cluster < 0 ? rt::kHostClusterAuto : 0) | (ctx->hs.nquad > 0 ? rt::kHostQuad : 0) |
                    (ctx->hs.nshell > 0 && ctx->brute_direct != 0 ? rt::kHostDirect : 0) |
-                   (ctx->hs.diffuse_only && ctx->brute_lean != 0 ? rt::kHostLean : 0);
+                   (ctx->hs.diffuse_only && ctx->brute_lean != 0 ? rt::kHostLean : 0) |
+                   (ctx->brute_primary != 0 ? rt::kHostPrimary : 0);
     s.nsingle = ctx->hs.nsingle;
     s.shell = ctx->hs.nshell > 0 ? 2 * s.ncslot : 0;
     s.near_floor = s.shell && ctx->brute_near != 0 ? ctx->hs.shell_floor : 0.0f;
@@ -490,6 +492,7 @@ const std::vector<Option>& options() {
         {"brute_direct", &rt_ctx::brute_direct, range(-1, 1), "brute_direct must be -1 (auto), 0 (off) or 1 (auto)", repack},
         // the flag reaches launch_pick in DevScene::host_flags, made for every launch: nothing is packed or uploaded
         {"brute_lean", &rt_ctx::brute_lean, range(-1, 1), "brute_lean must be -1 (auto), 0 (off) or 1 (auto)", none},
+        {"brute_primary", &rt_ctx::brute_primary, range(-1, 1), "brute_primary must be -1 (auto), 0 (off) or 1 (auto)", none},
         {"bvh", &rt_ctx::bvh_layout, range(RT_BVH_REFERENCE, RT_BVH_SAH), "bvh must be 0 (reference tree) or 1 (sah)", repack},
         {"brute_cluster", &rt_ctx::brute_cluster, range(-1, 1), "brute_cluster must be -1 (auto), 0 (off) or 1 (force)", repack},
         {"brute_shell", &rt_ctx::brute_shell, range(-1, 1), "brute_shell must be -1 (auto), 0 (off) or 1 (force)", repack},
@@ -2018,14 +2021,14 @@ int rt_debug_shell_word(rt_ctx* ctx) {
     return w;
 }
 
-int rt_debug_last_launch(int32_t out[20]) {
+int rt_debug_last_launch(int32_t out[21]) {
     if (!out) return RT_ERR_ARG;
     const rt::LaunchNote n = rt::last_launch();
     const rt::KernelKey& k = n.key;
-    const int64_t v[20] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
+    const int64_t v[21] = {k.trav, k.count, k.log,  k.smem,       k.ovf,    k.resume, k.step, k.wide,          k.brute,
                            k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds,
-                           n.shell, n.near, n.quad};
-    for (int i = 0; i < 20; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+                           n.shell, n.near, n.quad, n.primary};
+    for (int i = 0; i < 21; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
     return RT_OK;
 }
 

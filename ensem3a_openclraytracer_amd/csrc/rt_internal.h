@@ -16,6 +16,7 @@ constexpr int32_t kHostClusterAuto = 1;   // option "brute_cluster" is -1: only 
 constexpr int32_t kHostDirect = 4;        // ... and the enable of the in-place test (option "brute_direct"; rt_debug_last_direct)
 constexpr int32_t kHostQuad = 2;          // the shell's record has split faces (option "brute_quad"; rt_debug_last_launch)
 constexpr int32_t kHostLean = 8;          // every material emissive or diffuse (HostScene::diffuse_only) and option "brute_lean" not 0
+constexpr int32_t kHostPrimary = 16;      // option "brute_primary" not 0: a lean sliced launch traces its camera rays in a pre-pass
 struct DevScene {
     // FAST traversal: BVH2 nodes holding both child boxes, 4 x float4 each:
     //   [0] = c0.min.x, c0.max.x, c0.min.y, c0.max.y
@@ -309,11 +310,15 @@ struct KernelKey {
     int brute;    // render_kernel's BRUTE_: 0 none, 1 lock-step, 2 teams, 3 clustered, | kBruteSliced | kBruteRefill
     int ts;       // resumable walk: lanes per pixel (1, 2, 4, 8)
     int acc;      // 0 one-shot, kAccAdd, kAccListed
+    // render_kernel's BRUTE_ bits above kBruteLean (option "brute_primary"; a field of its own: brute keeps its five
+    // bits): 0 the kernels above, 1 a lean sliced loop that starts every job from its pixel's record
+    // (kBrutePrimary), 2 the pre-pass that writes those records (kBrutePrepass)
+    int primary = 0;
 };
 inline bool operator==(const KernelKey& a, const KernelKey& b) {
     return a.trav == b.trav && a.count == b.count && a.log == b.log && a.smem == b.smem && a.ovf == b.ovf &&
            a.resume == b.resume && a.step == b.step && a.wide == b.wide && a.brute == b.brute && a.ts == b.ts &&
-           a.acc == b.acc;
+           a.acc == b.acc && a.primary == b.primary;
 }
 // The lean form of the one-lane brute-force kernels (render_kernel's BRUTE_ bit kBruteLean; option "brute_lean"): a
 // loop without the glossy, glass, IBL and pilot code, for the launches whose frame cannot reach any of it.  A launch
@@ -326,6 +331,14 @@ inline bool operator==(const KernelKey& a, const KernelKey& b) {
 //   spp > 0, max_bounce >= 0 the loop's "no sample" and "no bounce" exits are not compiled in;
 //   fixed_point, sun_cache   on, their default: the lean loop has them on at compile time.
 constexpr int kBruteLean = 16;
+// ... and of a lean sliced launch, the form whose camera rays a pre-pass traces (option "brute_primary", -1 or 1 auto,
+// 0 off; kHostPrimary): the pre-pass kernel (kBrutePrepass: render_kernel's staging prologue, then one camera ray per
+// tile pixel) writes every pixel's slice record -- slice_publish's layout, zero samples done, the camera hit, the
+// ray's direction; "all done" for a padding pixel -- and its samples-done word, and the loop kernel (kBrutePrimary)
+// starts every job from its pixel's record: no pixel arithmetic, no camera_dir and no PRIMARY trip in the loop.
+// Only the template argument carries the two bits; a key has them in KernelKey::primary
+constexpr int kBrutePrimary = 32;
+constexpr int kBrutePrepass = 64;
 inline bool brute_lean_frame(int32_t host_flags, const FrameParams& fp) {
     uint32_t e4;
     std::memcpy(&e4, &fp.env[4], sizeof e4);
@@ -392,6 +405,7 @@ struct LaunchNote {
     int near;    // ... with a non-zero floor in its face tests (DevScene::near_floor != 0)
     int quad;    // ... and split faces in its record (option "brute_quad")
     int direct;  // ... and the in-place test of the first record enabled in it (option "brute_direct")
+    int primary; // the launch's camera rays were traced by a pre-pass (option "brute_primary"; KernelKey::primary 1)
 };
 void note_launch(const LaunchNote& n);
 LaunchNote last_launch();

@@ -68,6 +68,10 @@ constexpr int kBruteRefill = 8;
 // or diffuse, no IBL term, one pass, fixed_point and sun_cache on -- whose loop holds none of the glossy, glass, IBL
 // and pilot code and reads no flag that the rule has fixed.  Every operation that shapes a bit stays: the frame is
 // the general kernel's
+// ... and + kBrutePrimary (32) / kBrutePrepass (64; rt_internal.h) for the lean sliced launches whose camera rays a
+// pre-pass traces: kBrutePrepass | loop is that pre-pass -- this kernel's staging prologue, so the trace reads the
+// records the loop kernel's trace reads, then one camera ray per tile pixel, its hit written as the pixel's slice
+// record -- and + kBrutePrimary the loop that starts every job from such a record
 template <int TRAV, bool COUNT, bool LOG = false, bool SMEM = false, bool OVF = false, int BRUTE_ = 0, int ACC = 0>
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel at 96 VGPRs, i.e. 5 waves per SIMD
 // (one register more costs a wave per SIMD and ~10 % on C2); the product instantiations fit without
@@ -87,6 +91,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     constexpr bool LEAN = (BRUTE_ & kBruteLean) != 0;
     static_assert(!LEAN || ((BRUTE == 1 || BRUTE == 3) && TRAV == TRAV_FAST && !COUNT && !LOG && !ACC && RT_SHADE_ROWS),
                   "lean: the one-lane one-shot product kernels");
+    constexpr bool PRE = (BRUTE_ & kBrutePrimary) != 0;       // every job starts from its pixel's record
+    constexpr bool PREPASS = (BRUTE_ & kBrutePrepass) != 0;   // the kernel that writes those records
+    static_assert(!PRE || (LEAN && SLICED), "camera rays in a pre-pass: the lean sliced kernels");
+    static_assert(!PREPASS || (BRUTE_ == (kBrutePrepass | 1) || BRUTE_ == (kBrutePrepass | 3)), "the pre-pass: one per loop");
+    static_assert(!PREPASS || (TRAV == TRAV_FAST && !COUNT && !LOG && !SMEM && !OVF && !ACC && RT_SHADE_ROWS), "the pre-pass: a product kernel");
     extern __shared__ __attribute__((aligned(16))) int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
@@ -185,6 +194,39 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
     const unsigned long long team_leaders = ts == 1 ? ~0ull : ts == 2 ? 0x5555555555555555ull
                                              : ts == 4 ? 0x1111111111111111ull : 0x0101010101010101ull;
 
+    // The pre-pass of a lean sliced launch (kBrutePrepass; launch_pick runs it between make_const_kernel and the loop
+    // kernel): for tile pixel p what the loop's hand-out and PRIMARY trip do for a new pixel -- the frame pixel i, its
+    // camera ray, that ray's trace over the records staged above (the loop kernel's layout and the loop's trace: the
+    // same bits) -- written as the pixel's slice record in slice_publish's layout: no sample done, no shadow ray
+    // cached.  A padding pixel (i >= npix: a partial last row) gets "all done", what its slice 0 publishes in the
+    // other sliced kernels.  Plain stores: the kernel boundary orders them before the loop kernel's loads, and every
+    // launch writes every record and every samples-done word of its tile (no memset, nothing kept from a frame)
+    if constexpr (PREPASS) {
+        for (int64_t p0 = (int64_t)blockIdx.x * B; p0 < F.nloc; p0 += (int64_t)gridDim.x * B) {
+            const int64_t pp = p0 + threadIdx.x;
+            if (pp >= F.nloc) continue;
+            const int krow = (int)pp / W;
+            const int col = (int)pp - krow * W;
+            const int64_t i64 = ((int64_t)F.row0 + (int64_t)krow * F.row_step) * W + col;
+            float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 1000.0f), r2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            uint32_t i0 = 0, w0 = 0, s0 = (uint32_t)spp;
+            if (i64 < F.npix) {
+                const rtm_f3 d = camera_dir(C, W, (int)i64);
+                const Hit h = trace<TRAV, COUNT, SMEM, OVF, true, BRUTE == 3>(S, nodes, tris, C.position, d, stk, B, lst, c, mtrec, ts, boxrec);
+                r0.w = h.k;
+                r2 = make_float4(d.x, d.y, d.z, 0.0f);
+                i0 = (uint32_t)i64;
+                w0 = (uint32_t)(h.tri + 1);   // (| (sun0 + 2) << 16 with sun0 = -2)
+                s0 = 0u;
+            }
+            float4* st = F.slice_state + 3 * pp;
+            st[0] = r0;                                                                             // acc.xyz | kc
+            st[1] = make_float4(__uint_as_float(i0), 0.0f, __uint_as_float(w0), __uint_as_float(s0));   // seed0 seed1 | w s
+            st[2] = r2;                                                                             // cd
+            F.slice_ready[pp] = s0;
+        }
+    }
+
     int phase = FETCH;
     PixelQueue pq;
     pq.per = (F.handout && (LEAN || F.pass != 2)) ? (unsigned)(((ACC == kAccListed ? (int64_t)nloc : F.nloc) + kGroups - 1) / kGroups) : 0u;   // pass 2: cost order, interleaved
@@ -247,7 +289,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
                       (unsigned)(tc + 1) | ((unsigned)(sun0 + 2) << 16), s, true, cdv);
     };
 
-    while (true) {
+    while (!PREPASS) {   // (the pre-pass has run its own loop, above: it goes on to the stamps' flush)
         if constexpr (STAMPS) chain_stamp(stamp_wl, kStampRest);
         // instrumented build: wave cycles in the trace (cyc_trav) and in the rest of the loop (cyc_shade:
         // every iteration's time, the trace's subtracted below; unsigned wrap-around cancels)
@@ -276,11 +318,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
             refill_ev++;
             refill_lanes += (unsigned)__popcll(need);
         }
+        // PRE: a job whose record the pre-pass wrote (a whole pixel, or slice 0) -- complete before the launch, so it
+        // is read below without a poll
+        [[maybe_unused]] bool first = false;
         if (need) {
             unsigned sl = kWholeJob;   // SLICED: the job's slice, or a whole pixel
             unsigned int q;
             if constexpr (SLICED) q = take_job<kRefill>(pq, need, team_lane0, work_counter, nloc, lane, nsl, stail, sl);
             else q = take_pixel<kRefill>(pq, need, team_lane0, work_counter, nloc, lane);
+            if constexpr (PRE) {
+                // every job starts from its pixel's record (below), which holds all that depends on the pixel's
+                // number: lim is the slice whose end the job stops at -- the last one for a whole job, send(K - 1) =
+                // spp -- and s the count that a job of slice k > 0 waits for.  A padding pixel's record says "all done"
+                if (phase == FETCH) {
+                    if (q < nloc) {
+                        p = (int)q;
+                        first = sl == kWholeJob || sl == 0;
+                        lim = sl == kWholeJob ? (int)nsl - 1 : (int)sl;
+                        s = send(sl - 1u);   // (unused by a first job)
+                        phase = WAIT_SLICE;
+                    } else {
+                        phase = DONE;
+                    }
+                }
+            } else
             if (SLICED && phase == FETCH && q < nloc && sl != kWholeJob && sl > 0) {
                 // continues a pixel once its slice sl - 1 is done (below): all it needs is in that slice's state
                 p = (int)q;
@@ -353,7 +414,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         if constexpr (SLICED) {
             // the previous slice's samples done, published by the lane that ran it (save_slice): once the
             // count is there the job continues from that lane's state, in this same iteration
-            if (phase == WAIT_SLICE && slice_ready(F, p, (unsigned)s)) {
+            bool take = false;
+            if constexpr (PRE) take = phase == WAIT_SLICE && (first || slice_ready(F, p, (unsigned)s));
+            else take = phase == WAIT_SLICE && slice_ready(F, p, (unsigned)s);
+            if (take) {
                 unsigned w;
                 gu64* st = (gu64*)(F.slice_state + 3 * (int64_t)p);
                 slice_take(st, acc, kc, seed0, seed1, w, s);
@@ -473,8 +537,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         }
 
         // -- one ray per busy lane --
-        const rtm_f3 to = (phase == PRIMARY) ? C.position : Bo;
-        const rtm_f3 td = (phase == PRIMARY) ? cd : ((phase == BOUNCE) ? Bd : C.sun);
+        // (PRE: no lane is ever in PRIMARY -- the pre-pass traced the camera rays)
+        const rtm_f3 to = (!PRE && phase == PRIMARY) ? C.position : Bo;
+        const rtm_f3 td = (!PRE && phase == PRIMARY) ? cd : ((phase == BOUNCE) ? Bd : C.sun);
         const unsigned long long t_tr = COUNT ? clock64() : 0;
         if constexpr (STAMPS) chain_stamp(stamp_wl, kStampHead);
         const Hit h = trace<TRAV, COUNT, SMEM, OVF, BRUTE != 0, BRUTE == 3>(S, nodes, tris, to, td, stk, B, lst, c, mtrec, ts, boxrec);
@@ -485,7 +550,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_REN
         }
         ++cost;
         bool finish = false;
-        if (phase == PRIMARY) {
+        if (!PRE && phase == PRIMARY) {
             tc = h.tri;
             kc = h.k;
             tri = tc; j = 0;
@@ -1137,7 +1202,8 @@ struct KernelRow {
 // A row's key is made from the template arguments that name its kernel: the two cannot disagree.
 template <int TRAV, bool COUNT, bool LOG, bool SMEM, bool OVF, int BRUTE_>
 KernelRow render_row() {
-    return {KernelKey{TRAV, COUNT, LOG, SMEM, OVF, 0, 1, 0, BRUTE_, 1, kTuAcc},
+    // (BRUTE_'s bits above kBruteLean are the key's primary: 1 kBrutePrimary, 2 kBrutePrepass)
+    return {KernelKey{TRAV, COUNT, LOG, SMEM, OVF, 0, 1, 0, BRUTE_ & (kBrutePrimary - 1), 1, kTuAcc, BRUTE_ / kBrutePrimary},
             (const void*)render_kernel<TRAV, COUNT, LOG, SMEM, OVF, BRUTE_, kTuAcc>};
 }
 template <bool COUNT, bool LOG, bool SMEM, bool OVF, bool STEP, int WIDE, int TS>
@@ -1203,6 +1269,16 @@ void lean_rows(std::vector<KernelRow>& t) {
         t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteLean>());
         t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteRefill | kBruteLean>());
         t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteRefill | kBruteLean>());
+    }
+}
+// ... and behind them the lean sliced kernels that start every job from a record, and the pre-pass that writes the
+// records (option "brute_primary")
+template <int LOOP>
+void primary_rows(std::vector<KernelRow>& t) {
+    if constexpr (RT_SHADE_ROWS && !kTuAcc) {
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteLean | kBrutePrimary>());
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBruteSliced | kBruteRefill | kBruteLean | kBrutePrimary>());
+        t.push_back(render_row<TRAV_FAST, false, false, false, false, LOOP | kBrutePrepass>());
     }
 }
 
@@ -1426,6 +1502,8 @@ const void* kernel_fn(const KernelKey& k) {
         engine_rows<false>(t);
         lean_rows<3>(t);
         lean_rows<1>(t);
+        primary_rows<3>(t);
+        primary_rows<1>(t);
         return t;
     }();
     for (const KernelRow& r : table)
@@ -1489,6 +1567,10 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     // ... and so is the lean loop of an all-diffuse one-shot frame (rt_internal.h: the rule; one-shot kernels only, so
     // rt_accum.hip's and rt_adaptive.hip's translation units hold none)
     if (RT_SHADE_ROWS && !kTuAcc && brute_lean_kernel(k, f.team) && brute_lean_frame(sc.host_flags, f)) k.brute |= kBruteLean;
+    // ... and of a lean sliced launch, the loop that starts every job from the record a pre-pass wrote (below; option
+    // "brute_primary" not 0, kHostPrimary).  Lean and sliced only: the records' buffer is then there (setup_slices),
+    // and every other launch keeps its kernel and gains no launch
+    if ((k.brute & kBruteLean) && bslices && (sc.host_flags & kHostPrimary)) k.primary = 1;
     if (brute && f.team <= 1) lds = brute_lds_bytes(sc, block, false);
     const void* fn = kernel_fn(k);
     // the grid stays within what the device keeps resident (not that the slices' hand-off needs it: a job is only
@@ -1497,18 +1579,31 @@ hipError_t launch_pick(const DevScene& sc, const FrameParams& fp, KernelKey k, i
     const int64_t grid = std::min(need, resident(fp.max_waves));
     if (e != hipSuccess) return e;
     // the samples-done words of the tile's pixels (the tree walk's are zeroed by setup_slices)
-    if (bslices) e = hipMemsetAsync(f.slice_ready, 0, (size_t)fp.nloc * sizeof(uint32_t), stream);
+    // (a launch with a pre-pass: the pre-pass writes them)
+    if (bslices && !k.primary) e = hipMemsetAsync(f.slice_ready, 0, (size_t)fp.nloc * sizeof(uint32_t), stream);
     const LaunchConst* lc = nullptr;
     if (e == hipSuccess) e = setup_work_block(f, d_work, stream, &lc);
     if (e != hipSuccess) return e;
     const int shell = (k.brute & 3) == 3 && sc.shell != 0;
     note_launch({k, f.team, f.walk_team, f.slices, f.refill, grid, lds, shell, shell && sc.near_floor != 0.0f,
-                 shell && (sc.host_flags & kHostQuad) != 0, shell && (sc.host_flags & kHostDirect) != 0});
+                 shell && (sc.host_flags & kHostQuad) != 0, shell && (sc.host_flags & kHostDirect) != 0, k.primary});
 #if RT_CHAIN_STAMPS
     if (!d_counts) d_counts = chain_stamp_buffer();   // (nullptr when the allocation failed: the kernel then adds nothing)
 #endif
     DevScene a0 = sc;
     void* args[] = {&a0, &f, &d_out, &d_counts, &d_work, &lc};
+    if (k.primary) {
+        // the pre-pass, behind make_const_kernel on the launch's stream and before the loop kernel: the same arguments
+        // and LDS (it stages what the loop kernel stages), a resident grid that strides over the tile's pixels
+        KernelKey kp = k;
+        kp.brute &= 3;
+        kp.primary = 2;
+        const void* fpre = kernel_fn(kp);
+        const int64_t gpre = std::min((fp.nloc + block - 1) / block, resident_blocks(fpre, block, lds, fp.max_waves, &e));
+        if (e != hipSuccess) return e;
+        e = hipLaunchKernel(fpre, dim3((unsigned)gpre), dim3(block), args, lds, stream);
+        if (e != hipSuccess) return e;
+    }
     return hipLaunchKernel(fn, dim3((unsigned)grid), dim3(block), args, lds, stream);
 }
 

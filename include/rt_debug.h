@@ -237,8 +237,10 @@ int rt_debug_last_slices(void);
  * parameters; out[15] = blocks launched, out[16] = bytes of dynamic LDS per block; out[17] = 1 when the kernel
  * walked a shell (option "brute_shell": the clustered loop on a scene that has one), else 0; out[18] = 1 when it
  * walked that shell with a non-zero floor (option "brute_near"), else 0; out[19] = 1 when that shell's record has
- * split walls (option "brute_quad"), else 0. */
-int rt_debug_last_launch(int32_t out[20]);
+ * split walls (option "brute_quad"), else 0; out[20] = 1 when a pre-pass traced the launch's camera rays and its
+ * kernel started every job from the record of its pixel (option "brute_primary": -1 or 1 auto, 0 off; the lean
+ * sliced launches), else 0 -- a field of its own: the key's brute is the same with the option on and off. */
+int rt_debug_last_launch(int32_t out[21]);
 
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
