@@ -491,6 +491,105 @@ class KernelLauncher(object):
         return {"rgb": total / count.to(torch.float32)[:, None], "sum": total, "n": count,
                 "k": state[:, 3].view(torch.float32), "tri": tri, "hit": tri >= 0, "state": state}
 
+    @staticmethod
+    def _lens_args(cam, npix, jitter, aperture, focus, seed, first, count):
+        """The checked camera, lens and pixel range of ``lens_frame`` / ``lens_rays`` (rt_api.h's argument rules)."""
+        cam = _native.f32(cam).reshape(-1)
+        if cam.size < 10:
+            raise ValueError("cam needs 10 floats")
+        npix, first = int(npix), int(first)
+        count = npix - first if count is None else int(count)
+        if npix < 1 or first < 0 or count < 0 or first + count > npix:
+            raise ValueError(f"pixels {first} .. +{count} outside the frame of {npix}")
+        jitter, aperture, focus = float(jitter), float(aperture), float(focus)
+        if not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError("jitter must be finite and >= 0")
+        if not (np.isfinite(aperture) and aperture >= 0.0):
+            raise ValueError("aperture must be finite and >= 0")
+        if not (np.isfinite(focus) and focus > 0.0):
+            raise ValueError("focus must be finite and > 0")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError("seed must be a uint32")
+        return cam[:10], _native.Lens(jitter, aperture, focus, seed), npix, first, count
+
+    def lens_rays(self, cam, npix, jitter, aperture, focus, seed, first=0, count=None, sample0=0, nsamples=1):
+        """The sample rays of a lens frame (rt_lens_rays of rt_api.h): float32 ``[count, nsamples, 8]``, ray
+        ``[t, q]`` that of pixel ``first + t`` and sample ``sample0 + q`` -- direction, origin, then the pixel's
+        frame seeds as uint bits.  Needs no scene."""
+        cam, lens, npix, first, count = self._lens_args(cam, npix, jitter, aperture, focus, seed, first, count)
+        sample0, nsamples = int(sample0), int(nsamples)
+        if sample0 < 0 or nsamples < 1:
+            raise ValueError("sample0 must be >= 0 and nsamples >= 1")
+        return self._ctx.lens_rays(cam, lens, npix, first, count, sample0, nsamples)
+
+    def lens_frame(self, cam, env, npix, spp, max_bounce, jitter=1.0, aperture=0.0, focus=1.0, seed=0, first=0,
+                   count=None, state=None) -> dict:
+        """A frame whose every sample goes down a camera ray of its own (rt_lens_radiance of rt_api.h): ``jitter``
+        is the width in pixels of the box filter the samples are spread over (anti-aliasing), ``aperture`` the
+        radius of a thin lens and ``focus`` the distance of the plane in focus along the view axis (depth of
+        field); ``seed`` selects the rays' uniforms.  ``jitter = 0, aperture = 0`` is ``launch_Raytracing``'s
+        frame, bit for bit.  Pixels ``first .. first + count - 1`` of ``cam``'s frame of ``npix`` are rendered.
+
+        Returns ``rgb`` (the clamped frame ``[count, 3]``), ``sum``, ``n`` and ``state``.  Passing the returned
+        ``state`` back adds ``spp`` more samples to every pixel: after calls of ``a`` and ``b`` samples the result
+        is that of one call of ``a + b``.  A numpy state (or none) goes through the blocking host form, split over
+        the launcher's devices; a torch int32 ``[count, 8]`` tensor on the launcher's first device goes through
+        the device form on torch's current stream, is updated in place, and the results are tensors there (nothing
+        is copied to the host and the call does not wait); ``lens_state`` makes the tensor a frame starts from."""
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be >= 1")
+        e = _native.f32(env).reshape(-1)
+        if e.size < 5:
+            raise ValueError("env needs 5 floats")
+        cam, lens, npix, first, count = self._lens_args(cam, npix, jitter, aperture, focus, seed, first, count)
+        if state is not None and hasattr(state, "data_ptr"):
+            import torch
+            if state.dtype != torch.int32 or not state.is_contiguous():
+                raise TypeError("state must be a contiguous int32 tensor")
+            if tuple(state.shape) != (count, 8) or not state.is_cuda:
+                raise ValueError(f"state must be [{count}, 8] on the launcher's device, got {list(state.shape)}")
+            stream = torch.cuda.current_stream(state.device).cuda_stream
+            if count:
+                self._ctx.lens_radiance_device(0, cam, e[:5], lens, npix, first, count, spp, int(max_bounce),
+                                               _native.RT_RADIANCE_RESUME, state.data_ptr(), stream)
+            rgb = torch.empty((count, 3), dtype=torch.float32, device=state.device)
+            if count:
+                self._ctx.radiance_resolve_device(0, state.data_ptr(), count, rgb.data_ptr(), stream)
+            return {"rgb": rgb, "sum": state[:, 0:3].view(torch.float32), "n": state[:, 7], "state": state}
+        if state is not None:
+            if not isinstance(state, np.ndarray) or state.dtype != _native.RADIANCE_STATE_DTYPE:
+                raise TypeError("state must be the 'state' array an earlier call returned")
+            if state.shape != (count,):
+                raise ValueError(f"state holds {state.size} records, needs {count}")
+            state = np.ascontiguousarray(state)
+        st = self._ctx.lens_radiance(cam, e[:5], lens, npix, first, count, spp, int(max_bounce), state=state)
+        n = st["n"].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = st["sum"] / n.astype(np.float32)[:, None]
+        rgb = np.fmax(np.fmin(mean, np.float32(1.0)), np.float32(0.0))   # Raytracing.cl:211-220: NaN goes to 1
+        return {"rgb": rgb, "sum": st["sum"].copy(), "n": n, "state": st}
+
+    @staticmethod
+    def lens_state(npix, first=0, count=None, device="cuda"):
+        """The records a lens frame starts from, as a torch int32 ``[count, 8]`` tensor for ``lens_frame``'s device
+        form: ``sum = 0``, ``n = 0`` and the frame's seeds ``(i % npix, i / npix)``.  Resuming these is the fresh
+        call, bit for bit, so a device-resident loop passes this tensor to its first ``lens_frame`` and the same
+        tensor to every later one."""
+        import torch
+        npix, first = int(npix), int(first)
+        count = npix - first if count is None else int(count)
+        if npix < 1 or first < 0 or count < 0 or first + count > npix:
+            raise ValueError(f"pixels {first} .. +{count} outside the frame of {npix}")
+        state = torch.zeros((count, 8), dtype=torch.int32, device=device)
+        i = torch.arange(first, first + count, dtype=torch.int64, device=device)
+        state[:, 4] = (i % npix).to(torch.int32)
+        state[:, 5] = (i // npix).to(torch.int32)
+        state[:, 3] = torch.tensor(1000.0, dtype=torch.float32).view(torch.int32).item()   # k of a miss
+        state[:, 6] = -1
+        return state
+
     def launch_ImgProcessing(self, h_src, h_out, SIZE):
         """Gamma 2.2 of ``ImgProcessing.cl``: ``h_out[k] = min(h_src[k], 1) ** 2.2`` for ``k < 3*SIZE*SIZE``."""
         src = _native.f32(h_src).reshape(-1)

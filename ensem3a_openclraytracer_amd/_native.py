@@ -38,6 +38,7 @@ EXPORTED = (
     "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
     "rt_trace", "rt_trace_device",
     "rt_radiance", "rt_radiance_device", "rt_camera_rays", "rt_camera_rays_device",
+    "rt_lens_radiance", "rt_lens_radiance_device", "rt_lens_rays", "rt_lens_rays_device", "rt_radiance_resolve_device",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_trace_clustered", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
@@ -98,6 +99,16 @@ RADIANCE_STATE_DTYPE = np.dtype([("sum", np.float32, (3,)), ("k", np.float32), (
                                  ("seed1", np.uint32), ("tri", np.int32), ("n", np.int32)])
 RT_RADIANCE_RESUME = 1
 RT_ACCUM_MAX_SAMPLES = 1 << 24
+
+
+class Lens(ctypes.Structure):
+    """rt_lens of rt_api.h: the box filter's width in pixels, the lens's radius, the distance of the plane in focus
+    and the seed of the sample rays' uniforms."""
+    _fields_ = [("jitter", ctypes.c_float), ("aperture", ctypes.c_float), ("focus", ctypes.c_float),
+                ("seed", ctypes.c_uint32)]
+
+    def __init__(self, jitter: float = 1.0, aperture: float = 0.0, focus: float = 1.0, seed: int = 0):
+        super().__init__(float(jitter), float(aperture), float(focus), int(seed) & 0xffffffff)
 
 
 def pack_radiance_rays(origins, directions, seeds=None) -> np.ndarray:
@@ -212,6 +223,12 @@ def lib():
             "rt_radiance_device": (_i32, [_c_p, _i32, _c_p, _i64, _c_p, _i32, _i32, _i32, _c_p, _c_p]),
             "rt_camera_rays": (_i32, [_c_p, _c_p, _i64, _i64, _i64, _c_p]),
             "rt_camera_rays_device": (_i32, [_c_p, _i32, _c_p, _i64, _i64, _i64, _c_p, _c_p]),
+            "rt_lens_radiance": (_i32, [_c_p, _c_p, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _i32, _c_p]),
+            "rt_lens_radiance_device": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _i32, _c_p,
+                                               _c_p]),
+            "rt_lens_rays": (_i32, [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p]),
+            "rt_lens_rays_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p, _c_p]),
+            "rt_radiance_resolve_device": (_i32, [_c_p, _i32, _c_p, _i64, _c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -626,6 +643,67 @@ class Context:
         self._check(lib().rt_camera_rays_device(self.handle, int(device_index), ptr(c), int(npix), int(first),
                                                 int(count), _c_p(int(rays_ptr)) if rays_ptr else None,
                                                 self._stream(stream_ptr)))
+
+    # -- lens frames (rt_lens_radiance*, rt_lens_rays*, rt_radiance_resolve_device) --
+    def lens_radiance(self, cam, env, lens: Lens, npix: int, first: int, count: int, spp: int, max_bounce: int,
+                      state: np.ndarray = None) -> np.ndarray:
+        """rt_lens_radiance: pixels ``first .. first + count - 1`` -> a ``RADIANCE_STATE_DTYPE`` array ``[count]``,
+        blocking.  ``state`` (such an array, updated in place and returned) resumes its records."""
+        c, e = f32(cam).reshape(-1), f32(env).reshape(-1)
+        if c.size < 10 or e.size < 5:
+            raise ValueError("cam needs 10 floats and env 5")
+        count = int(count)
+        flags = 0
+        if state is not None:
+            if not isinstance(state, np.ndarray) or state.dtype != RADIANCE_STATE_DTYPE or not state.flags.c_contiguous:
+                raise TypeError("state must be a C-contiguous RADIANCE_STATE_DTYPE numpy array")
+            if state.shape != (count,):
+                raise ValueError(f"state has shape {list(state.shape)}, needs [{count}]")
+            flags = RT_RADIANCE_RESUME
+        else:
+            state = np.zeros(max(count, 0), RADIANCE_STATE_DTYPE)
+        self._check(lib().rt_lens_radiance(self.handle, ptr(c), ptr(e), ctypes.byref(lens), int(npix), int(first), count,
+                                           int(spp), int(max_bounce), flags, state.ctypes.data if count > 0 else None))
+        return state
+
+    def lens_radiance_device(self, device_index: int, cam, env, lens: Lens, npix: int, first: int, count: int,
+                             spp: int, max_bounce: int, flags: int, state_ptr: int, stream_ptr: int = 0) -> None:
+        """rt_lens_radiance_device: device records on slot ``device_index``, enqueued on the stream; never waits."""
+        c, e = f32(cam).reshape(-1), f32(env).reshape(-1)
+        if c.size < 10 or e.size < 5:
+            raise ValueError("cam needs 10 floats and env 5")
+        self._check(lib().rt_lens_radiance_device(self.handle, int(device_index), ptr(c), ptr(e), ctypes.byref(lens),
+                                                  int(npix), int(first), int(count), int(spp), int(max_bounce),
+                                                  int(flags), _c_p(int(state_ptr)) if state_ptr else None,
+                                                  self._stream(stream_ptr)))
+
+    def lens_rays(self, cam, lens: Lens, npix: int, first: int = 0, count: int = None, sample0: int = 0,
+                  nsamples: int = 1) -> np.ndarray:
+        """rt_lens_rays: float32 ``[count, nsamples, 8]`` rays (with the pixels' seeds)."""
+        c = f32(cam).reshape(-1)
+        if c.size < 10:
+            raise ValueError("cam needs 10 floats")
+        count = int(npix) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), max(int(nsamples), 0), RAY_FLOATS), np.float32)
+        self._check(lib().rt_lens_rays(self.handle, ptr(c), ctypes.byref(lens), int(npix), int(first), count,
+                                       int(sample0), int(nsamples), out.ctypes.data if out.size else None))
+        return out
+
+    def lens_rays_device(self, device_index: int, cam, lens: Lens, npix: int, first: int, count: int, sample0: int,
+                         nsamples: int, rays_ptr: int, stream_ptr: int = 0) -> None:
+        c = f32(cam).reshape(-1)
+        if c.size < 10:
+            raise ValueError("cam needs 10 floats")
+        self._check(lib().rt_lens_rays_device(self.handle, int(device_index), ptr(c), ctypes.byref(lens), int(npix),
+                                              int(first), int(count), int(sample0), int(nsamples),
+                                              _c_p(int(rays_ptr)) if rays_ptr else None, self._stream(stream_ptr)))
+
+    def radiance_resolve_device(self, device_index: int, state_ptr: int, n: int, rgb_ptr: int,
+                                stream_ptr: int = 0) -> None:
+        """rt_radiance_resolve_device: ``n`` device records -> ``3 * n`` clamped floats, enqueued on the stream."""
+        self._check(lib().rt_radiance_resolve_device(self.handle, int(device_index),
+                                                     _c_p(int(state_ptr)) if state_ptr else None, int(n),
+                                                     _c_p(int(rgb_ptr)) if rgb_ptr else None, self._stream(stream_ptr)))
 
     def rgb8(self, src, gamma: bool = False, out=None) -> np.ndarray:
         """Host float32 -> uint8 through the device output stage."""

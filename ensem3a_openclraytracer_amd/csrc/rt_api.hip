@@ -1879,6 +1879,182 @@ int rt_camera_rays(rt_ctx* ctx, const float cam[10], int64_t npix, int64_t first
     return RT_OK;
 }
 
+// ---- lens frames (rt_lens_radiance*, rt_lens_rays*, rt_radiance_resolve_device) ----
+static_assert(sizeof(rt_lens) == 16, "rt_lens is four 32-bit words");
+namespace {
+// the lens, beside camera_rays_check's camera and pixel range
+int lens_check(rt_ctx* ctx, const rt_lens* lens) {
+    if (!lens) return set_err(ctx, RT_ERR_ARG, "lens must not be NULL");
+    if (!std::isfinite(lens->jitter) || lens->jitter < 0.0f)
+        return set_err(ctx, RT_ERR_ARG, "lens jitter must be finite and >= 0, got %g", (double)lens->jitter);
+    if (!std::isfinite(lens->aperture) || lens->aperture < 0.0f)
+        return set_err(ctx, RT_ERR_ARG, "lens aperture must be finite and >= 0, got %g", (double)lens->aperture);
+    if (!std::isfinite(lens->focus) || !(lens->focus > 0.0f))
+        return set_err(ctx, RT_ERR_ARG, "lens focus must be finite and > 0, got %g", (double)lens->focus);
+    return RT_OK;
+}
+
+rt::LensOptions lens_options(const rt_lens* lens) {
+    rt::LensOptions o;
+    o.jitter = lens->jitter;
+    o.aperture = lens->aperture;
+    o.focus = lens->focus;
+    o.seed = lens->seed;
+    return o;
+}
+
+// the checks the two lens render entry points share: rt_camera_rays' on the camera and the pixels, the lens, then
+// rt_radiance's on the rest (whose ray array is the state here: there is none to pass)
+int lens_radiance_check(rt_ctx* ctx, const float* cam, const float* env, const rt_lens* lens, int64_t npix,
+                        int64_t first, int64_t count, int spp, int max_bounce, int flags, const void* state) {
+    int st = camera_rays_check(ctx, cam, npix, first, count, cam);   // (a NULL state is radiance_check's to report)
+    if (!st) st = lens_check(ctx, lens);
+    if (!st) st = radiance_check(ctx, state, count, env, spp, max_bounce, flags, state);
+    return st;
+}
+
+int lens_radiance_enqueue(rt_ctx* ctx, Device& d, const float cam[10], const float env[5], const rt_lens* lens,
+                          int64_t npix, int64_t first, int64_t count, int spp, int max_bounce, int flags,
+                          rt_radiance_state* d_state, hipStream_t s) {
+    const rt::DevScene sc = dev_scene(ctx, d);
+    if (!rt::radiance_fits(sc, ctx->traversal, ctx->block))
+        return set_err(ctx, RT_ERR_SCENE, "a traversal stack of %d entries per lane does not fit a block of 64 lanes",
+                       ctx->traversal == RT_TRAVERSAL_REF ? (int)sc.ref_stack : (int)sc.depth);
+    HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
+    rt::RadianceOptions q{};
+    std::memcpy(q.env, env, sizeof q.env);
+    q.spp = spp;
+    q.max_bounce = max_bounce;
+    // radiance_enqueue's flags; the launch drops fixed_point and sun_cache unless the lens is degenerate
+    q.flags = (flags & RT_RADIANCE_RESUME ? 1 : 0) |
+              (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite ? 2 : 0) |
+              (ctx->fixed_point ? 4 : 0) | (ctx->fixed_point && ctx->sun_cache ? 8 : 0);
+    q.grid_cap = ctx->radiance_grid;
+    q.max_waves = ctx->max_waves;
+    q.block = ctx->block;
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_lens_radiance(sc, ctx->traversal, cam, npix, first, count, (float4*)d_state,
+                                             lens_options(lens), q, d.rad_work.p, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int lens_rays_check(rt_ctx* ctx, const float* cam, const rt_lens* lens, int64_t npix, int64_t first, int64_t count,
+                    int sample0, int nsamples, const void* rays) {
+    int st = camera_rays_check(ctx, cam, npix, first, count, rays);
+    if (!st) st = lens_check(ctx, lens);
+    if (st) return st;
+    if (sample0 < 0) return set_err(ctx, RT_ERR_ARG, "sample0 %d < 0", sample0);
+    if (nsamples < 1) return set_err(ctx, RT_ERR_ARG, "nsamples %d < 1", nsamples);
+    if (count * (int64_t)nsamples >= ((int64_t)1 << 31))
+        return set_err(ctx, RT_ERR_ARG, "%lld rays in one call: 2^31 or more", (long long)(count * (int64_t)nsamples));
+    return RT_OK;
+}
+
+int lens_rays_enqueue(rt_ctx* ctx, Device& d, const float cam[10], const rt_lens* lens, int64_t npix, int64_t first,
+                      int64_t count, int sample0, int nsamples, float* d_rays, hipStream_t s) {
+    HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_lens_rays(cam, npix, first, count, sample0, nsamples, lens_options(lens),
+                                         (float4*)d_rays, d.rad_work.p, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+}  // namespace
+
+int rt_lens_radiance_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5], const rt_lens* lens,
+                            int64_t npix, int64_t first, int64_t count, int spp, int max_bounce, int flags,
+                            rt_radiance_state* d_state, void* stream) {
+    Device* dp = nullptr;
+    int st = lens_radiance_check(ctx, cam, env, lens, npix, first, count, spp, max_bounce, flags, d_state);
+    if (!st) st = slot_of(ctx, device_index, &dp);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    if ((uintptr_t)d_state & 15) return set_err(ctx, RT_ERR_ARG, "d_state must be 16-byte aligned");
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    return lens_radiance_enqueue(ctx, *dp, cam, env, lens, npix, first, count, spp, max_bounce, flags, d_state,
+                                 (hipStream_t)stream);
+}
+
+int rt_lens_radiance(rt_ctx* ctx, const float cam[10], const float env[5], const rt_lens* lens, int64_t npix,
+                     int64_t first, int64_t count, int spp, int max_bounce, int flags, rt_radiance_state* state) {
+    const int st = lens_radiance_check(ctx, cam, env, lens, npix, first, count, spp, max_bounce, flags, state);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    // contiguous chunks over the slots; every slot is enqueued before any is waited for
+    const int64_t nd = (int64_t)ctx->devs.size();
+    for (int64_t k = 0; k < nd; ++k) {
+        const int64_t b = count * k / nd, m = count * (k + 1) / nd - b;
+        if (m <= 0) continue;
+        Device& d = ctx->devs[k];
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, grow(d, d.rad_state, (size_t)m * sizeof(rt_radiance_state)));
+        if (flags & RT_RADIANCE_RESUME)
+            HIP_OR_RET(ctx, hipMemcpyAsync(d.rad_state.p, state + b, (size_t)m * sizeof(rt_radiance_state),
+                                           hipMemcpyHostToDevice, d.stream));
+        const int qs = lens_radiance_enqueue(ctx, d, cam, env, lens, npix, first + b, m, spp, max_bounce, flags,
+                                             (rt_radiance_state*)d.rad_state.p, d.stream);
+        if (qs) return qs;
+        HIP_OR_RET(ctx, hipMemcpyAsync(state + b, d.rad_state.p, (size_t)m * sizeof(rt_radiance_state),
+                                       hipMemcpyDeviceToHost, d.stream));
+    }
+    for (auto& d : ctx->devs) {
+        HIP_OR_RET(ctx, hipSetDevice(d.id));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    }
+    return RT_OK;
+}
+
+int rt_lens_rays_device(rt_ctx* ctx, int device_index, const float cam[10], const rt_lens* lens, int64_t npix,
+                        int64_t first, int64_t count, int sample0, int nsamples, float* d_rays, void* stream) {
+    Device* dp = nullptr;
+    int st = lens_rays_check(ctx, cam, lens, npix, first, count, sample0, nsamples, d_rays);
+    if (!st) st = slot_of(ctx, device_index, &dp);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    if ((uintptr_t)d_rays & 15) return set_err(ctx, RT_ERR_ARG, "d_rays must be 16-byte aligned");
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    return lens_rays_enqueue(ctx, *dp, cam, lens, npix, first, count, sample0, nsamples, d_rays, (hipStream_t)stream);
+}
+
+int rt_lens_rays(rt_ctx* ctx, const float cam[10], const rt_lens* lens, int64_t npix, int64_t first, int64_t count,
+                 int sample0, int nsamples, float* rays) {
+    const int st = lens_rays_check(ctx, cam, lens, npix, first, count, sample0, nsamples, rays);
+    if (st) return st;
+    if (count == 0) return RT_OK;
+    Device& d = ctx->devs[0];
+    const size_t bytes = (size_t)count * (size_t)nsamples * 32;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, grow(d, d.q_rays, bytes));
+    const int qs = lens_rays_enqueue(ctx, d, cam, lens, npix, first, count, sample0, nsamples, (float*)d.q_rays.p,
+                                     d.stream);
+    if (qs) return qs;
+    HIP_OR_RET(ctx, hipMemcpyAsync(rays, d.q_rays.p, bytes, hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_radiance_resolve_device(rt_ctx* ctx, int device_index, const rt_radiance_state* d_state, int64_t n,
+                               float* d_rgb, void* stream) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (n < 0 || n >= ((int64_t)1 << 31)) return set_err(ctx, RT_ERR_ARG, "record count %lld out of range", (long long)n);
+    if (n > 0 && (!d_state || !d_rgb)) return set_err(ctx, RT_ERR_ARG, "d_state / d_rgb must not be NULL");
+    Device* dp = nullptr;
+    const int st = slot_of(ctx, device_index, &dp);
+    if (st) return st;
+    if (n == 0) return RT_OK;
+    const uintptr_t s0 = (uintptr_t)d_state, o0 = (uintptr_t)d_rgb;
+    if ((s0 & 15) || (o0 & 3)) return set_err(ctx, RT_ERR_ARG, "d_state must be 16-byte and d_rgb 4-byte aligned");
+    if (s0 < o0 + (uintptr_t)n * 12 && o0 < s0 + (uintptr_t)n * sizeof(rt_radiance_state))
+        return set_err(ctx, RT_ERR_ARG, "d_state and d_rgb must not overlap");
+    HIP_OR_RET(ctx, hipSetDevice(dp->id));
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, order_after_last(*dp, s));
+    HIP_OR_RET(ctx, rt::launch_resolve((const float4*)d_state, n, d_rgb, s));
+    HIP_OR_RET(ctx, mark_launch(*dp, s));
+    return RT_OK;
+}
+
 int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* out, int64_t n) {
     if (!ctx || !x || !out || n < 0) return set_err(ctx, RT_ERR_ARG, "bad arguments");
     Device& d = ctx->devs[0];

@@ -393,6 +393,24 @@ hipError_t launch_radiance(const DevScene& sc, int traversal, const float4* rays
                            const RadianceOptions& q, void* work, hipStream_t stream);
 hipError_t launch_camera_rays(const float cam[10], int64_t npix, int64_t first, int64_t count, float4* rays,
                               void* work, hipStream_t stream);
+// the scene as the radiance kernels walk it and the largest block <= `block` whose stack fits (0: none does)
+int radiance_fit(const DevScene& sc, int trav, int block, DevScene* out);
+// Lens frames (rt_lens_radiance*, rt_lens_rays*, rt_radiance_resolve_device, rt_api.h; kernels in rt_lens.hip's
+// translation unit): pixels first .. first + count - 1 of cam's frame of npix pixels, spp samples each down a ray of
+// its own (lens_ray of rt_api.h) -> count state records, under launch_radiance's engines, options and work block
+// (RadianceOptions::flags as rt_radiance.hip's; fixed_point and sun_cache are dropped unless the lens is degenerate).
+// launch_lens_rays writes the rays of samples sample0 .. sample0 + nsamples - 1 of those pixels, [count][nsamples]
+// rays of two float4; launch_resolve the clamped means of n records, three floats each.
+struct LensOptions {
+    float jitter, aperture, focus;
+    uint32_t seed;
+};
+hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float cam[10], int64_t npix, int64_t first,
+                                int64_t count, float4* state, const LensOptions& lens, const RadianceOptions& q,
+                                void* work, hipStream_t stream);
+hipError_t launch_lens_rays(const float cam[10], int64_t npix, int64_t first, int64_t count, int sample0,
+                            int nsamples, const LensOptions& lens, float4* rays, void* work, hipStream_t stream);
+hipError_t launch_resolve(const float4* state, int64_t n, float* rgb, hipStream_t stream);
 // test hooks
 // The process's last render launch (launch_pick) as its kernel got it: the refined key, FrameParams::team,
 // walk_team, slices and refill (0: every lane refilled at once), the grid and the dynamic LDS bytes

@@ -271,6 +271,8 @@ __global__ void __launch_bounds__(256) camera_rays_kernel(const LaunchConst* __r
                                           __uint_as_float((uint32_t)(i / npix)));
 }
 
+}  // namespace
+
 // the scene as the radiance kernel walks it (the plain form of launch_query: no persistent-grid overflow buffer,
 // the whole FAST stack in LDS) and the largest block <= `block` whose stack fits; 0: none does
 int radiance_fit(const DevScene& sc, int trav, int block, DevScene* out) {
@@ -282,8 +284,6 @@ int radiance_fit(const DevScene& sc, int trav, int block, DevScene* out) {
     if (out) *out = s2;
     return block;
 }
-
-}  // namespace
 
 size_t radiance_work_bytes() { return kRadConstOffset + sizeof(LaunchConst); }
 

@@ -352,6 +352,85 @@ int rt_camera_rays(rt_ctx* ctx, const float cam[10], int64_t npix, int64_t first
 int rt_camera_rays_device(rt_ctx* ctx, int device_index, const float cam[10], int64_t npix, int64_t first,
                           int64_t count, float* d_rays, void* stream);
 
+/* Lens frames: a frame whose every sample goes down a camera ray of its own, generated on the device -- a box-filter
+ * jitter of the pixel (anti-aliased edges) and a thin lens (depth of field) -- and summed into the pixel's
+ * rt_radiance_state record (no counterpart in the reference, which sends all samples of a pixel down genCameraRay(i)).
+ *
+ * Definition of the sample ray, lens_ray(cam, lens, i, s), for pixel i and sample index s (the number of samples the
+ * pixel has had, counted from 0) -- everything is fp32, evaluated in the order written, and nothing is contracted
+ * except the fmafs shown:
+ *   Uniforms, counter-based, uint32 arithmetic modulo 2^32:
+ *          h(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *          base = h(h(seed) ^ (uint32)i) + 4 * (uint32)s
+ *          u_k  = (float)(h(base + k) >> 8) * 2^-24        k = 0..3, each in [0, 1), exact
+ *      The integrator's own RNG chain is not touched: a pixel keeps the frame's seeds (i % npix, i / npix), and the
+ *      chain runs on from sample to sample as Raytracing.cl:171-172, 191-209 runs it.
+ *   Jitter, with pixelX, pixelY, pas, position and focal as genCameraRay has them (Raytracing.cl:18-37):
+ *          jx = (u0 - 0.5f) * jitter;  jy = (u1 - 0.5f) * jitter
+ *          pc = ( fmaf((float)pixelY + jx, pas, -0.5f),  0,  fmaf(-((float)pixelX + jy), pas, 0.5f) )
+ *          d  = normalize((position + pc) - focal)
+ *      jitter is the width of a box filter in pixels; jitter == 0 adds +-0 and gives genCameraRay's bits, no branch.
+ *   Lens, in the camera's local frame, before the three rotations.  aperture == 0 (a branch): the pinhole, the ray is
+ *      (position, d).  Otherwise
+ *          r = sqrt(u2) * aperture;  (sn, cs) = sincos(6.2831855f * u3);  l = (r * cs, 0, r * sn)
+ *          t = focus / d.y;  d = normalize(d * t - l)
+ *      and the origin's offset is l.  focus is the distance along the view axis (local +y) from position to the plane
+ *      in focus; aperture the lens's radius.
+ *   Rotations: d, and l when there is a lens, go through genCameraRay's three rotations (about x by cam[3], y by
+ *      cam[4], z by cam[5]) as it applies them; the origin is position + rotated l.
+ *
+ * The frame: a call processes pixels first .. first + count - 1 of cam's frame of npix pixels for spp samples and
+ * leaves one record per pixel.  For each sample s in order: trace lens_ray(i, s) under the context's "traversal", run
+ * one naiveGI sample from that hit with the pixel's running seeds, add it to sum (a float3 add), increment n.  The
+ * record: sum; seed0, seed1 the RNG words after the last sample; n; k, tri the first hit of the LAST sample's ray, as
+ * rt_trace reports it.  A fresh call starts from sum = 0, n = 0 and the seeds (i % npix, i / npix).  With
+ * RT_RADIANCE_RESUME sum, n and the seeds come from the record, so s continues from the record's n; tri and k of the
+ * record are never read: every sample traces its own ray, no index comes from the caller's data.  The frame is
+ * fmax(fmin(sum / (float)n, 1), 0) (rt_radiance_resolve_device).
+ * Contracts, bit for bit:
+ *   A  the record equals a sequence of S fresh rt_radiance queries at spp = 1, one per sample s = 0 .. S - 1, of the
+ *      single ray lens_ray(i, s), each with the seeds the query before left (the frame's for s = 0), the sums added
+ *      in order in fp32; k, tri and the seeds are the last query's;
+ *   B  with jitter = 0 and aperture = 0 the records are rt_radiance's records of rt_camera_rays at the same spp, in
+ *      all 32 bytes, so the frame is rt_render's;
+ *   C  calls of a then b samples with RT_RADIANCE_RESUME leave the records of one call of a + b;
+ *   D  the host form equals the device form, and nothing depends on "block", "radiance_grid", the engine or how the
+ *      pixels are split over the device slots.
+ * A camera that makes non-finite rays is safe, as non-finite rays are for rt_radiance.
+ *
+ *   rt_lens_radiance            host records, blocking: contiguous chunks of the pixels over the device slots, every
+ *                               slot enqueued before any is waited for.
+ *   rt_lens_radiance_device     DEVICE records (16-byte aligned) on slot device_index, enqueued on `stream`; never
+ *                               waits.
+ *   rt_lens_rays                the rays of samples sample0 .. sample0 + nsamples - 1 of the pixels, [count][nsamples][8]
+ *                               floats in rt_camera_rays' layout: dir.xyz, origin.xyz, then the pixel's frame seeds,
+ *                               the same for every sample, so sample 0's ray can go to rt_radiance as it is.  Host
+ *                               array, blocking (device 0).  Needs no scene.
+ *   rt_lens_rays_device         the same into a 16-byte aligned device array, enqueued on `stream`.
+ *   rt_radiance_resolve_device  d_rgb[3 * n] = fmax(fmin(sum / (float)n, 1), 0) of n records of rt_radiance_device or
+ *                               rt_lens_radiance_device, with the IEEE division (n = 0 gives NaN, which the clamp
+ *                               sends to 1); enqueued on `stream`, never waits: from records to a frame, and on to
+ *                               rt_rgb8_device, without the host.
+ * Ordering with the context's other work follows rt_trace; a call leaves an open accumulation untouched and valid.
+ * The engines and "block" / "radiance_grid" are rt_radiance's.
+ * RT_ERR_STATE: no scene, no environment, or "traversal" is FAST and the scene has no FAST layout.  RT_ERR_SCENE: the
+ * BVH2 stack does not fit a block of 64 lanes.  RT_ERR_ARG: rt_radiance's and rt_camera_rays' argument checks; a NULL
+ * lens; a jitter or aperture that is not finite or is negative; a focus that is not finite and > 0; sample0 < 0;
+ * nsamples < 1; count * nsamples >= 2^31; pixels outside the frame; misaligned device arrays (rt_radiance_resolve_
+ * device: d_rgb 4-byte aligned, no overlap).  count == 0 (n == 0) is RT_OK and launches nothing. */
+typedef struct { float jitter, aperture, focus; uint32_t seed; } rt_lens;   /* 16 bytes */
+int rt_lens_radiance(rt_ctx* ctx, const float cam[10], const float env[5], const rt_lens* lens, int64_t npix,
+                     int64_t first, int64_t count, int spp, int max_bounce, int flags, rt_radiance_state* state);
+int rt_lens_radiance_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5], const rt_lens* lens,
+                            int64_t npix, int64_t first, int64_t count, int spp, int max_bounce, int flags,
+                            rt_radiance_state* d_state, void* stream);
+int rt_lens_rays(rt_ctx* ctx, const float cam[10], const rt_lens* lens, int64_t npix, int64_t first, int64_t count,
+                 int sample0, int nsamples, float* rays);
+int rt_lens_rays_device(rt_ctx* ctx, int device_index, const float cam[10], const rt_lens* lens, int64_t npix,
+                        int64_t first, int64_t count, int sample0, int nsamples, float* d_rays, void* stream);
+int rt_radiance_resolve_device(rt_ctx* ctx, int device_index, const rt_radiance_state* d_state, int64_t n,
+                               float* d_rgb, void* stream);
+
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,
  * [3] = environment lookups, [4] = stack overflows (REF traversal drops),
