@@ -47,7 +47,8 @@ class Progressive(object):
     """A frame that takes more samples (``KernelLauncher.begin_progressive``; rt_accum_* of rt_api.h).
 
     Every ``add`` returns a finished frame at the samples done so far -- the frame ``launch_Raytracing``
-    renders at that ``spp``, bit for bit -- and costs only the samples it adds.
+    renders at that ``spp``, bit for bit -- and costs only the samples it adds.  Opened by
+    ``begin_progressive_lens`` it is a lens frame instead: read ``lens_frame`` for ``launch_Raytracing`` below.
     """
 
     def __init__(self, ctx: "_native.Context", imgDim: int):
@@ -333,6 +334,33 @@ class KernelLauncher(object):
         if getattr(self, "_progressive", None) is not None:
             self._progressive._open = False   # replaced: the context holds one accumulation
         self._ctx.accum_begin(cam[:10], env[:5], imgDim, int(maxBounce))
+        self._progressive = Progressive(self._ctx, imgDim)
+        return self._progressive
+
+    def begin_progressive_lens(self, h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_light_data,
+                               h_BVH, h_cam, h_envData, imgDim, maxBounce, h_IBL, jitter: float = 1.0,
+                               aperture: float = 0.0, focus: float = 1.0, seed: int = 0) -> "Progressive":
+        """``begin_progressive`` for a lens frame (rt_accum_begin_lens of rt_api.h): every sample goes down a camera
+        ray of its own -- ``jitter``, ``aperture``, ``focus`` and ``seed`` as ``lens_frame`` takes them -- so the
+        frames that ``add``, ``refine`` and ``denoised`` return have anti-aliased edges and depth of field.  A pixel
+        that has received ``n`` samples holds ``lens_frame``'s value at ``spp = n``, bit for bit; ``jitter = 0,
+        aperture = 0`` is ``begin_progressive``.  The guides describe the pixel-centre pinhole ray's first hit,
+        whatever the lens: with ``aperture > 0`` the filter under-smooths edges that are out of focus."""
+        imgDim = int(imgDim)
+        cam = _native.f32(h_cam).reshape(-1)
+        env = _native.f32(h_envData).reshape(-1)
+        if cam.size < 10 or env.size < 5:
+            raise ValueError("h_cam needs 10 floats and h_envData 5")
+        if imgDim < 1:
+            raise ValueError("imgDim must be >= 1")
+        _, lens, _, _, _ = self._lens_args(cam, imgDim, jitter, aperture, focus, seed, 0, None)
+        if h_light_data is not None:
+            np.asarray(h_light_data)  # accepted for signature compatibility (unused by the kernel)
+        self._upload_scene(h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_BVH)
+        self._upload_env(h_IBL)
+        if getattr(self, "_progressive", None) is not None:
+            self._progressive._open = False   # replaced: the context holds one accumulation
+        self._ctx.accum_begin_lens(cam[:10], env[:5], lens, imgDim, int(maxBounce))
         self._progressive = Progressive(self._ctx, imgDim)
         return self._progressive
 

@@ -39,6 +39,7 @@ EXPORTED = (
     "rt_trace", "rt_trace_device",
     "rt_radiance", "rt_radiance_device", "rt_camera_rays", "rt_camera_rays_device",
     "rt_lens_radiance", "rt_lens_radiance_device", "rt_lens_rays", "rt_lens_rays_device", "rt_radiance_resolve_device",
+    "rt_accum_begin_lens", "rt_accum_begin_lens_device", "rt_debug_accum_state",
     "rt_bvh_build", "rt_device_count", "rt_debug_math", "rt_debug_fn", "rt_debug_trace", "rt_debug_trace_clustered", "rt_debug_scene_info", "rt_debug_pixel_log",
     "rt_debug_wave_counts", "rt_debug_quantise_axis", "rt_debug_timings", "rt_debug_brute_layout",
     "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
@@ -229,6 +230,9 @@ def lib():
             "rt_lens_rays": (_i32, [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p]),
             "rt_lens_rays_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i64, _i64, _i32, _i32, _c_p, _c_p]),
             "rt_radiance_resolve_device": (_i32, [_c_p, _i32, _c_p, _i64, _c_p, _c_p]),
+            "rt_accum_begin_lens": (_i32, [_c_p, _c_p, _c_p, _c_p, _i64, _i32]),
+            "rt_accum_begin_lens_device": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64, _i32, _i32, _i32]),
+            "rt_debug_accum_state": (_i32, [_c_p, _c_p]),
             "rt_bvh_build": (_i32, [_c_p, _i64, _c_p, _i64, _c_p, ctypes.POINTER(_i64)]),
             "rt_device_count": (_i32, []),
             "rt_obj_parse": (_i32, [_c_p, _i64, ctypes.POINTER(_c_p)]),
@@ -477,6 +481,31 @@ class Context:
         c, e = f32(cam), f32(env)
         self._check(lib().rt_accum_begin_device(self.handle, int(device_index), ptr(c), ptr(e), int(npix),
                                                 int(max_bounce), int(row0), int(row_step)))
+
+    # -- progressive lens frames (rt_accum_begin_lens*): every other accum_* call works on whichever kind is open --
+    def accum_begin_lens(self, cam, env, lens: "Lens", npix: int, max_bounce: int) -> None:
+        c, e = f32(cam), f32(env)
+        if c.size != 10 or e.size != 5:
+            raise ValueError("cam must have 10 floats and envData 5")
+        self._check(lib().rt_accum_begin_lens(self.handle, ptr(c), ptr(e),
+                                              ctypes.byref(lens) if lens is not None else None, int(npix),
+                                              int(max_bounce)))
+        self._accum_npix = int(npix)
+
+    def accum_begin_lens_device(self, cam, env, lens: "Lens", npix, max_bounce, row0, row_step,
+                                device_index: int = 0) -> None:
+        c, e = f32(cam), f32(env)
+        self._check(lib().rt_accum_begin_lens_device(self.handle, int(device_index), ptr(c), ptr(e),
+                                                     ctypes.byref(lens) if lens is not None else None, int(npix),
+                                                     int(max_bounce), int(row0), int(row_step)))
+
+    def debug_accum_state(self) -> np.ndarray:
+        """rt_debug_accum_state: the open host accumulation's records, a ``RADIANCE_STATE_DTYPE`` array ``[npix]``
+        in frame order (blocking; nothing is rendered)."""
+        n = getattr(self, "_accum_npix", 0)
+        out = np.zeros(max(n, 1), RADIANCE_STATE_DTYPE)
+        self._check(lib().rt_debug_accum_state(self.handle, out.ctypes.data))
+        return out[:n]
 
     def accum_add_device(self, spp: int, d_out_ptr: int, stream_ptr: int = 0, device_index: int = 0) -> None:
         self._check(lib().rt_accum_add_device(self.handle, int(device_index), int(spp), _c_p(int(d_out_ptr)),

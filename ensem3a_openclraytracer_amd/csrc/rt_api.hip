@@ -81,6 +81,14 @@ struct Device {
     float acc_cam[10] = {0}, acc_env[5] = {0};
     int64_t acc_npix = 0, acc_nloc = 0, acc_samples = 0;
     int acc_max_bounce = 0, acc_row0 = 0, acc_row_step = 1;
+    // A lens accumulation (rt_accum_begin_lens*): every sample down lens_ray(cam, acc_lens_opt, i, s), the state
+    // initialised by begin so that every add resumes.  centre: the first hit of every tile pixel's pixel-centre
+    // pinhole ray, (k, tri) in 8 bytes, which the guides read (a lens record's k, tri are its last sample's);
+    // traced by the first rt_accum_guides* of the accumulation, dropped by begin, end and invalidation
+    bool acc_lens = false;
+    rt::LensOptions acc_lens_opt{};
+    DevBuf centre;
+    bool acc_centre_ready = false;
     // Adaptive sampling (rt_accum_mark, rt_accum_select*, rt_accum_add_selected), each buffer allocated on first
     // use: the snapshot (acc.xyz, s: 16 bytes per pixel); the selection (SelView: list, length, compaction
     // scratch, 0/1 flags); and the list of every pixel, for a full add once the counts differ.  acc_samples is
@@ -414,6 +422,7 @@ void invalidate_accum(rt_ctx* ctx) {
         d.acc_valid = false;
         d.acc_marked = false;   // (mark and selection go with it)
         d.acc_selected = false;
+        d.acc_centre_ready = false;   // (and a lens accumulation's centre hits: the scene they were traced in is gone)
     }
 }
 
@@ -949,6 +958,25 @@ int render_host(rt_ctx* ctx, const float cam[10], const float env[5], int64_t np
     return st;
 }
 
+// What a launch of the radiance and lens kernels takes from the context: the render loop's exact shortcuts under the
+// conditions check_frame sets them (a lens launch drops fixed_point and sun_cache unless the lens is degenerate)
+rt::RadianceOptions radiance_options(const rt_ctx* ctx, const float env[5], int spp, int max_bounce, int flags) {
+    rt::RadianceOptions q{};
+    std::memcpy(q.env, env, sizeof q.env);
+    q.spp = spp;
+    q.max_bounce = max_bounce;
+    q.flags = (flags & RT_RADIANCE_RESUME ? 1 : 0) |
+              (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite ? 2 : 0) |
+              (ctx->fixed_point ? 4 : 0) | (ctx->fixed_point && ctx->sun_cache ? 8 : 0);
+    q.grid_cap = ctx->radiance_grid;
+    q.max_waves = ctx->max_waves;
+    q.block = ctx->block;
+    return q;
+}
+
+int lens_check(rt_ctx* ctx, const rt_lens* lens);   // (with the lens frames, below)
+rt::LensOptions lens_options(const rt_lens* lens);
+
 // ---- progressive accumulation (rt_accum_*) ----
 // begin and end: no mark, no selection, every pixel at the same count
 void accum_reset_selection(Device& d) {
@@ -965,11 +993,13 @@ int accum_close_slot(rt_ctx* ctx, Device& d) {
     d.acc_open = false;
     d.acc_valid = false;
     d.acc_samples = 0;
+    d.acc_lens = false;
+    d.acc_centre_ready = false;
     accum_reset_selection(d);
-    if (!d.accum.p && !d.mark.p && !d.sel.p && !d.all.p) return RT_OK;
+    if (!d.accum.p && !d.mark.p && !d.sel.p && !d.all.p && !d.centre.p) return RT_OK;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     if (d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));   // an add in flight still uses the state
-    for (DevBuf* b : {&d.accum, &d.mark, &d.sel, &d.all}) b->release();
+    for (DevBuf* b : {&d.accum, &d.mark, &d.sel, &d.all, &d.centre}) b->release();
     return RT_OK;
 }
 
@@ -1135,6 +1165,27 @@ int accum_gather_host(rt_ctx* ctx, void* out, size_t elem, const void* (*src)(De
     return RT_OK;
 }
 
+// the lens kernels keep a lane's whole traversal stack in LDS (rt_lens_radiance's rule)
+int lens_fits(rt_ctx* ctx, const rt::DevScene& sc, const char* what) {
+    const int trav = effective_traversal(ctx);
+    if (rt::radiance_fits(sc, trav, ctx->block)) return RT_OK;
+    return set_err(ctx, RT_ERR_SCENE, "%s: a traversal stack of %d entries per lane does not fit a block of 64 lanes",
+                   what, trav == RT_TRAVERSAL_REF ? (int)sc.ref_stack : (int)sc.depth);
+}
+
+// An add of a lens accumulation, on the stream the caller has ordered: spp samples of every tile pixel (list NULL)
+// or of the listed ones, each from its record's own count (the caller resolves the frame from the state)
+int accum_add_lens(rt_ctx* ctx, Device& d, const rt::FrameParams& fp, int spp, const uint32_t* list,
+                   const uint32_t* count, hipStream_t s) {
+    const rt::DevScene sc = dev_scene(ctx, d);
+    const rt::RadianceOptions q = radiance_options(ctx, d.acc_env, spp, d.acc_max_bounce, RT_RADIANCE_RESUME);
+    d.acc_valid = false;   // (an error below leaves the state undefined)
+    HIP_OR_RET(ctx, rt::launch_lens_accum(sc, effective_traversal(ctx), fp, (float4*)d.accum.p, list, count,
+                                          d.acc_lens_opt, q, d.rad_work.p, s));
+    d.acc_valid = true;
+    return RT_OK;
+}
+
 // the host forms: add spp samples on every slot (read: resolve the state instead, nothing rendered), then read
 // the frame back as render_host_ does (rgb8 >= 0: quantised on the devices first); out may be NULL for an add
 // (selected: rt_accum_add_selected -- the add runs on each slot's selection)
@@ -1188,6 +1239,8 @@ int rt_accum_begin_device(rt_ctx* ctx, int device_index, const float cam[10], co
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     d.acc_open = false;   // replaces the slot's accumulation
     d.acc_valid = false;
+    d.acc_lens = false;
+    d.acc_centre_ready = false;
     HIP_OR_RET(ctx, grow(d, d.accum, (size_t)fp.nloc * 2 * sizeof(float4)));
     std::memcpy(d.acc_cam, cam, sizeof d.acc_cam);
     std::memcpy(d.acc_env, env, sizeof d.acc_env);
@@ -1216,9 +1269,23 @@ int rt_accum_add_device(rt_ctx* ctx, int device_index, int spp, float* d_out, vo
                      d.acc_row_step, &fp);
     if (st) return st;
     if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
+    if (d.acc_lens && (st = lens_fits(ctx, dev_scene(ctx, d), "rt_accum_add")) != RT_OK) return st;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, order_after_last(d, s));
+    if (d.acc_lens) {
+        // a lens frame: the tile mapping of the lens loop, every pixel from its record's own count -- so the same
+        // launch whether or not the counts differ -- then the frame resolved from the state
+        if (fp.nloc > 0) {
+            st = accum_add_lens(ctx, d, fp, spp, nullptr, nullptr, s);
+            if (st) return st;
+            HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, d_out, fp.nloc, s));
+            HIP_OR_RET(ctx, mark_launch(d, s));
+        }
+        d.acc_samples += spp;
+        d.acc_full += spp;
+        return RT_OK;
+    }
     if (!d.acc_uniform && fp.nloc > 0) {
         // the pixels' counts differ (rt_accum_add_selected): the listed kernel over every pixel, each from its own
         // count, then the frame resolved from the state (pixel by pixel the divisor differs)
@@ -1259,6 +1326,47 @@ int rt_accum_begin(rt_ctx* ctx, const float cam[10], const float env[5], int64_t
     const int nd = (int)ctx->devs.size();
     for (int k = 0; k < nd; ++k) {
         st = rt_accum_begin_device(ctx, k, cam, env, npix, max_bounce, k, nd);
+        if (st) return st;
+    }
+    ctx->accum_host = true;
+    return RT_OK;
+}
+
+// A lens accumulation: rt_accum_begin_device's slot, then the lens and the records every add resumes from (the
+// initialisation runs on the slot's own stream; launches on other streams are ordered after it like any other)
+int rt_accum_begin_lens_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5],
+                               const rt_lens* lens, int64_t npix, int max_bounce, int row0, int row_step) {
+    rt::FrameParams fp;
+    Device* dp = nullptr;
+    int st = check_frame(ctx, cam, env, npix, 0, max_bounce, row0, row_step, &fp);
+    if (!st) st = lens_check(ctx, lens);
+    if (!st) st = slot_of(ctx, device_index, &dp);
+    if (!st) st = lens_fits(ctx, dev_scene(ctx, *dp), "rt_accum_begin_lens");
+    if (!st) st = rt_accum_begin_device(ctx, device_index, cam, env, npix, max_bounce, row0, row_step);
+    if (st) return st;
+    Device& d = *dp;
+    d.acc_open = false;   // (until the records are enqueued)
+    d.acc_valid = false;
+    HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
+    HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    HIP_OR_RET(ctx, rt::launch_lens_accum_init(fp, (float4*)d.accum.p, d.stream));
+    HIP_OR_RET(ctx, mark_launch(d, d.stream));
+    d.acc_lens = true;
+    d.acc_lens_opt = lens_options(lens);
+    d.acc_open = true;
+    d.acc_valid = true;
+    return RT_OK;
+}
+
+int rt_accum_begin_lens(rt_ctx* ctx, const float cam[10], const float env[5], const rt_lens* lens, int64_t npix,
+                        int max_bounce) {
+    rt::FrameParams fp;
+    int st = check_frame(ctx, cam, env, npix, 0, max_bounce, 0, 1, &fp);
+    if (!st) st = lens_check(ctx, lens);
+    if (st) return st;
+    const int nd = (int)ctx->devs.size();
+    for (int k = 0; k < nd; ++k) {
+        st = rt_accum_begin_lens_device(ctx, k, cam, env, lens, npix, max_bounce, k, nd);
         if (st) return st;
     }
     ctx->accum_host = true;
@@ -1345,15 +1453,21 @@ int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* 
     if (st) return st;
     if (!d_out && fp.nloc > 0) return set_err(ctx, RT_ERR_ARG, "d_out must not be NULL");
     if (fp.nloc <= 0) return RT_OK;
+    if (d.acc_lens && (st = lens_fits(ctx, dev_scene(ctx, d), "rt_accum_add_selected")) != RT_OK) return st;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, order_after_last(d, s));
     if (d.sel_known != 0) {   // (a selection the host knows to be empty adds nothing)
         const SelView v = sel_view(d);
-        d.acc_valid = false;   // (an error below leaves the state undefined)
-        HIP_OR_RET(ctx, rt::launch_accum_listed(dev_scene(ctx, d), fp, (float4*)d.accum.p, v.list, v.count,
-                                                effective_traversal(ctx), ctx->block, d_out, (unsigned int*)d.work.p, s));
-        d.acc_valid = true;
+        if (d.acc_lens) {   // the listed mapping of the lens loop over the same list
+            st = accum_add_lens(ctx, d, fp, spp, v.list, v.count, s);
+            if (st) return st;
+        } else {
+            d.acc_valid = false;   // (an error below leaves the state undefined)
+            HIP_OR_RET(ctx, rt::launch_accum_listed(dev_scene(ctx, d), fp, (float4*)d.accum.p, v.list, v.count,
+                                                    effective_traversal(ctx), ctx->block, d_out, (unsigned int*)d.work.p, s));
+            d.acc_valid = true;
+        }
         d.acc_samples += spp;
         if (!(d.sel_all && d.acc_uniform)) d.acc_uniform = false;
         else d.acc_full += spp;   // (every pixel, all at one count: a full add by another name)
@@ -1457,6 +1571,21 @@ int rt_accum_guides_device(rt_ctx* ctx, int device_index, float* d_guides, void*
     if (st) return st;
     hipStream_t s = (hipStream_t)stream;
     HIP_OR_RET(ctx, hipSetDevice(d.id));
+    if (d.acc_lens) {
+        // a lens record's k, tri are its last sample's hit: the guides' first hit is that of the pixel-centre pinhole
+        // ray, traced once per accumulation into d.centre -- the one case in which a guides call traces a ray
+        const rt::DevScene sc = dev_scene(ctx, d);
+        if (!d.acc_centre_ready && (st = lens_fits(ctx, sc, "rt_accum_guides")) != RT_OK) return st;
+        HIP_OR_RET(ctx, grow(d, d.centre, (size_t)d.acc_nloc * sizeof(float2)));
+        HIP_OR_RET(ctx, order_after_last(d, s));
+        if (!d.acc_centre_ready)
+            HIP_OR_RET(ctx, rt::launch_lens_centre(sc, effective_traversal(ctx), fp, (float2*)d.centre.p, d.rad_work.p, s));
+        HIP_OR_RET(ctx, rt::launch_lens_guides(sc, fp, (const float4*)d.accum.p, (const float2*)d.centre.p, d.rad_work.p,
+                                               (float4*)d_guides, s));
+        HIP_OR_RET(ctx, mark_launch(d, s));
+        d.acc_centre_ready = true;
+        return RT_OK;
+    }
     HIP_OR_RET(ctx, grow(d, d.dn_const, rt::launch_const_bytes()));
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_accum_guides(dev_scene(ctx, d), fp, (const float4*)d.accum.p, d.dn_const.p,
@@ -1767,17 +1896,7 @@ int radiance_enqueue(rt_ctx* ctx, Device& d, const float* d_rays, int64_t n, con
         return set_err(ctx, RT_ERR_SCENE, "a traversal stack of %d entries per lane does not fit a block of 64 lanes",
                        ctx->traversal == RT_TRAVERSAL_REF ? (int)sc.ref_stack : (int)sc.depth);
     HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
-    rt::RadianceOptions q{};
-    std::memcpy(q.env, env, sizeof q.env);
-    q.spp = spp;
-    q.max_bounce = max_bounce;
-    // the render loop's exact shortcuts, under the conditions check_frame sets them
-    q.flags = (flags & RT_RADIANCE_RESUME ? 1 : 0) |
-              (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite ? 2 : 0) |
-              (ctx->fixed_point ? 4 : 0) | (ctx->fixed_point && ctx->sun_cache ? 8 : 0);
-    q.grid_cap = ctx->radiance_grid;
-    q.max_waves = ctx->max_waves;
-    q.block = ctx->block;
+    const rt::RadianceOptions q = radiance_options(ctx, env, spp, max_bounce, flags);
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_radiance(sc, ctx->traversal, (const float4*)d_rays, (float4*)d_state, n, q, d.rad_work.p, s));
     HIP_OR_RET(ctx, mark_launch(d, s));
@@ -1921,17 +2040,7 @@ int lens_radiance_enqueue(rt_ctx* ctx, Device& d, const float cam[10], const flo
         return set_err(ctx, RT_ERR_SCENE, "a traversal stack of %d entries per lane does not fit a block of 64 lanes",
                        ctx->traversal == RT_TRAVERSAL_REF ? (int)sc.ref_stack : (int)sc.depth);
     HIP_OR_RET(ctx, grow(d, d.rad_work, rt::radiance_work_bytes()));
-    rt::RadianceOptions q{};
-    std::memcpy(q.env, env, sizeof q.env);
-    q.spp = spp;
-    q.max_bounce = max_bounce;
-    // radiance_enqueue's flags; the launch drops fixed_point and sun_cache unless the lens is degenerate
-    q.flags = (flags & RT_RADIANCE_RESUME ? 1 : 0) |
-              (ctx->sun_skip && env[3] == 0.0f && env[4] >= 0.0f && ctx->hs.colors_finite ? 2 : 0) |
-              (ctx->fixed_point ? 4 : 0) | (ctx->fixed_point && ctx->sun_cache ? 8 : 0);
-    q.grid_cap = ctx->radiance_grid;
-    q.max_waves = ctx->max_waves;
-    q.block = ctx->block;
+    const rt::RadianceOptions q = radiance_options(ctx, env, spp, max_bounce, flags);
     HIP_OR_RET(ctx, order_after_last(d, s));
     HIP_OR_RET(ctx, rt::launch_lens_radiance(sc, ctx->traversal, cam, npix, first, count, (float4*)d_state,
                                              lens_options(lens), q, d.rad_work.p, s));
@@ -2053,6 +2162,17 @@ int rt_radiance_resolve_device(rt_ctx* ctx, int device_index, const rt_radiance_
     HIP_OR_RET(ctx, rt::launch_resolve((const float4*)d_state, n, d_rgb, s));
     HIP_OR_RET(ctx, mark_launch(*dp, s));
     return RT_OK;
+}
+
+int rt_debug_accum_state(rt_ctx* ctx, rt_radiance_state* out) {
+    const int open = accum_host_open(ctx, "rt_debug_accum_state");
+    if (open) return open;
+    if (!out) return set_err(ctx, RT_ERR_ARG, "rt_debug_accum_state: out must not be NULL");
+    for (const auto& d : ctx->devs) {
+        const int st = accum_slot_usable(ctx, d, "rt_debug_accum_state");
+        if (st) return st;
+    }
+    return accum_gather_host(ctx, out, sizeof(rt_radiance_state), [](Device& d) { return (const void*)d.accum.p; });
 }
 
 int rt_debug_math(rt_ctx* ctx, int fn, const float* x, const float* y, float* out, int64_t n) {

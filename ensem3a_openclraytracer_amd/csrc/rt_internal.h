@@ -411,6 +411,25 @@ hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float c
 hipError_t launch_lens_rays(const float cam[10], int64_t npix, int64_t first, int64_t count, int sample0,
                             int nsamples, const LensOptions& lens, float4* rays, void* work, hipStream_t stream);
 hipError_t launch_resolve(const float4* state, int64_t n, float* rgb, hipStream_t stream);
+// Lens frames inside an accumulation (rt_accum_begin_lens*): the same loop over the tile-packed state
+// of fp's tile (fp: check_frame's camera, frame and rows; q.spp = the samples the add gives each job's pixel, on top
+// of the count its record holds -- every add resumes).
+//   launch_lens_accum_init  the records the tile's pixels start from: sum 0, n 0, the frame's seeds;
+//   launch_lens_accum       list NULL: a job per tile pixel; else the pixels list[0 .. *count) (ascending tile pixels,
+//                           *count a device word the kernel only reads, at most fp.nloc) -- launch_accum_listed's
+//                           list.  Padding pixels of a partial last row get no job;
+//   launch_lens_centre      centre[p] = (k, tri bits) of the first hit of tile pixel p's pixel-centre pinhole ray
+//                           (rt_camera_rays' ray, traced as rt_trace traces it), 8 bytes per tile pixel;
+//   launch_lens_guides      launch_accum_guides with the first hit read from `centre` in place of the state's words.
+// work: radiance_work_bytes(), as above.
+hipError_t launch_lens_accum_init(const FrameParams& fp, float4* state, hipStream_t stream);
+hipError_t launch_lens_accum(const DevScene& sc, int traversal, const FrameParams& fp, float4* state,
+                             const uint32_t* list, const uint32_t* count, const LensOptions& lens,
+                             const RadianceOptions& q, void* work, hipStream_t stream);
+hipError_t launch_lens_centre(const DevScene& sc, int traversal, const FrameParams& fp, float2* centre, void* work,
+                              hipStream_t stream);
+hipError_t launch_lens_guides(const DevScene& sc, const FrameParams& fp, const float4* state, const float2* centre,
+                              void* work, float4* d_guides, hipStream_t stream);
 // test hooks
 // The process's last render launch (launch_pick) as its kernel got it: the refined key, FrameParams::team,
 // walk_team, slices and refill (0: every lane refilled at once), the grid and the dynamic LDS bytes

@@ -2,7 +2,9 @@
 // sample goes down a camera ray of its own -- lens_ray(cam, lens, i, s), a box-filter jitter of the pixel and a thin
 // lens -- generated on the device and summed into the pixel's 32-byte state record.  A translation unit of its own,
 // like rt_radiance.hip: the instantiations below join no other module, so the code objects of every other kernel are
-// what they were without it.
+// what they were without it.  Lens frames inside an accumulation (rt_accum_begin_lens*) are further
+// instantiations of the same loop -- the tile and listed job mappings -- with three small kernels of their own: the
+// records a begin leaves, the centre-hit pass of the guides, and the guides from its buffer.
 //
 // The contract: a pixel's record is that of one fresh rt_radiance query per sample, of the ray
 // lens_ray(i, s) at spp = 1, each starting from the seeds the one before left, the sums added in order.  The loop
@@ -29,6 +31,29 @@ struct LensArgs {
     uint32_t hseed;   // h(seed)
     int W, npix, first;
 };
+
+// How a job index t of lens_radiance_kernel becomes a record slot p and a frame pixel i:
+//   kMapContig  p = t, i = first + t: rt_lens_radiance's slice of the frame;
+//   kMapTile    p = t, i = tile_pixel(p): the tile-packed state of an accumulation (rt_accum_add on a lens frame);
+//   kMapListed  p = list[t], i = tile_pixel(p), the job count read from the device word the compaction wrote
+//               (rt_accum_add_selected; a full add once the counts differ).
+// A tile job whose pixel is padding of a partial last row (i >= npix) is dropped at the refill, as is a listed p that
+// is no pixel of the tile: no index is used unchecked.
+constexpr int kMapContig = 0, kMapTile = 1, kMapListed = 2;
+struct LensJobs {   // what the tile and listed mappings add to LensArgs: wave-uniform (kMapContig reads none of it)
+    int row0, row_step;
+    unsigned nloc;            // records in the state
+    const uint32_t* list;     // kMapListed: tile pixels, ascending
+    const uint32_t* count;    // ... and how many
+};
+
+// pixel p of the tile of rows row0, row0 + row_step, ... -> the frame's pixel; false: padding of a partial last row
+__device__ __forceinline__ bool lens_tile_pixel(unsigned p, int W, int row0, int row_step, int npix, int* i) {
+    const unsigned krow = p / (unsigned)W;
+    const long long i64 = ((long long)row0 + (long long)krow * row_step) * W + (long long)(p - krow * (unsigned)W);
+    *i = (int)i64;
+    return i64 < npix;   // (npix < 2^31: check_frame)
+}
 
 // the uniforms' hash (rt_api.h): uint32 arithmetic modulo 2^32
 __host__ __device__ __forceinline__ uint32_t lens_hash(uint32_t x) {
@@ -79,15 +104,18 @@ __device__ __forceinline__ void lens_ray(const LaunchConst& C, const LensArgs& L
 // call's slice: one atomic reserves `chunk` consecutive pixels for the wave (query_walk_kernel's hand-out), its
 // refills hand them out in order.  A refill of a fresh call reads nothing (the seeds are the pixel's index); on
 // resume it reads the record's two float4, of which tri and k are dropped: every sample traces its own ray, so no
-// index comes from the caller's data.
+// index comes from the caller's data.  MAP (above): the tile and listed mappings always resume -- an accumulation's
+// records are initialised by its begin (lens_init_kernel) -- and carry the pixel i in a register from the refill, so
+// that no sample pays the mapping's division.
 // The traversal is trace<>, as radiance_kernel uses it.  sun_skip carries over (it does not depend on the ray);
 // fixed_point and sun_cache are set by the launch for the degenerate lens alone, whose samples share one ray.
 // amdgpu_waves_per_eu(5): the register allocator keeps the kernel within 96 VGPRs, radiance_kernel's 5 waves per
 // SIMD (left alone, the scheduler spreads the ray's evaluation over 102).
-template <int TRAV>
+template <int TRAV, int MAP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
-lens_radiance_kernel(DevScene S, LensArgs L, float4* __restrict__ state, unsigned n, int spp, int maxB, float e3, float e4,
-                     int flags, unsigned chunk, unsigned* __restrict__ counter, const LaunchConst* __restrict__ lconst) {
+lens_radiance_kernel(DevScene S, LensArgs L, float4* __restrict__ state, unsigned n_, int spp, int maxB, float e3, float e4,
+                     int flags, unsigned chunk, unsigned* __restrict__ counter, const LaunchConst* __restrict__ lconst,
+                     LensJobs J) {
     extern __shared__ __attribute__((aligned(16))) int lds_stack[];
     const int B = blockDim.x;
     int* stk = lds_stack + threadIdx.x;
@@ -95,13 +123,16 @@ lens_radiance_kernel(DevScene S, LensArgs L, float4* __restrict__ state, unsigne
     Cnt c{};
     const LaunchConst& C = *lconst;   // uniform: the camera, the sun vector and the IBL's rotations
     const int lane = threadIdx.x & 63;
-    const bool resume = (flags & kLensResume) != 0;
+    const bool resume = MAP != kMapContig || (flags & kLensResume) != 0;
+    // the jobs: the launch's count, or the list's length (never past the tile: list holds nloc words)
+    const unsigned n = MAP == kMapListed ? min(*J.count, J.nloc) : n_;
     const bool sun_skip = TRAV == TRAV_FAST && (flags & kLensSunSkip) != 0;
     const bool fixed_point = TRAV == TRAV_FAST && (flags & kLensFixedPoint) != 0;
     const bool sun_cache = TRAV == TRAV_FAST && (flags & kLensSunCache) != 0;
 
     int phase = FETCH;
-    unsigned idx = 0;
+    unsigned idx = 0;   // the lane's record slot p
+    int pix = 0;        // ... and its frame pixel i (kMapContig: first + idx, not kept)
     uint32_t seed0 = 0, seed1 = 0;
     rtm_f3 co = rtm_v3(0, 0, 0), cd = rtm_v3(0, 0, 1);   // the sample's ray
     float kc = 1000.0f;                                  // its hit
@@ -145,6 +176,12 @@ lens_radiance_kernel(DevScene S, LensArgs L, float4* __restrict__ state, unsigne
             } else {
                 wnext += cnt;
             }
+            if (MAP == kMapListed && phase == FETCH && valid) {
+                my = J.list[my];
+                valid = my < J.nloc;
+            }
+            if (MAP != kMapContig && phase == FETCH && valid)
+                valid = lens_tile_pixel(my, L.W, J.row0, J.row_step, L.npix, &pix);
             if (phase == FETCH && valid) {
                 idx = my;
                 sun0 = -2;
@@ -172,7 +209,7 @@ lens_radiance_kernel(DevScene S, LensArgs L, float4* __restrict__ state, unsigne
         if (phase == FETCH) continue;
 
         if (phase == GEN) {   // sample s of the pixel: its own ray, then its own first hit
-            lens_ray(C, L, L.first + (int)idx, (uint32_t)s, &co, &cd);
+            lens_ray(C, L, MAP == kMapContig ? L.first + (int)idx : pix, (uint32_t)s, &co, &cd);
             phase = PRIMARY;
         }
 
@@ -320,6 +357,96 @@ __global__ void __launch_bounds__(256) resolve_kernel(const float4* __restrict__
     rgb[3 * (size_t)t + 2] = fmaxf(fminf(u.z / cnt, 1.0f), 0.0f);
 }
 
+// rt_accum_begin_lens*: the records a tile's pixels start from -- sum 0, n 0, the frame's seeds (i % npix, i / npix),
+// the hit of a miss -- so that every add resumes (lens_state of KernelLauncher.py makes the same words)
+__global__ void __launch_bounds__(256) lens_init_kernel(float4* __restrict__ state, unsigned nloc, int W, int row0,
+                                                        int row_step, int npix) {
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nloc) return;
+    int i;
+    (void)lens_tile_pixel(p, W, row0, row_step, npix, &i);   // (a padding pixel's record is never read by a job)
+    state[2 * (size_t)p] = make_float4(0.0f, 0.0f, 0.0f, 1000.0f);
+    state[2 * (size_t)p + 1] = make_float4(__uint_as_float((uint32_t)(i % npix)), __uint_as_float((uint32_t)(i / npix)),
+                                           __int_as_float(-1), __int_as_float(0));
+}
+
+// The centre-hit pass of a lens accumulation's guides: genCameraRay(i) of every tile pixel -- camera_dir from the
+// camera's position, rt_camera_rays' ray -- traced as rt_trace's plain form traces it (query_plain_kernel: one thread
+// per ray, trace<>, the whole stack in LDS), (k, tri) as a record's PRIMARY step stores them; a padding pixel a miss.
+template <int TRAV>
+__global__ void __launch_bounds__(256) lens_centre_kernel(DevScene S, const LaunchConst* __restrict__ lconst, int W,
+                                                          int row0, int row_step, int npix, unsigned nloc,
+                                                          float2* __restrict__ centre) {
+    extern __shared__ int lds_stack[];
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nloc) return;
+    int i;
+    if (!lens_tile_pixel(p, W, row0, row_step, npix, &i)) {
+        centre[p] = make_float2(1000.0f, __int_as_float(-1));
+        return;
+    }
+    Cnt c{};
+    const LaunchConst& C = *lconst;
+    const Hit h = trace<TRAV, false>(S, S.nodes, S.tri_fast, C.position, camera_dir(C, W, i), lds_stack + threadIdx.x,
+                                     blockDim.x, lane_stack(S, lds_stack), c);
+    centre[p] = h.tri >= 0 ? make_float2(h.k, __int_as_float(h.tri)) : make_float2(1000.0f, __int_as_float(-1));
+}
+
+// A pixel's guides (rt_api.h: G0 = n | k, G1 = P | f, G2 = a | m) from the first hit (tc, kc) of its camera ray and
+// its sample count s; a miss keeps the pattern a fresh Guide has.  guides_kernel's evaluation (rt_denoise.hip),
+// operation by operation, restated here and not shared: sharing it through a header changes guides_kernel's
+// instruction schedule, and every code object but this one stays what it was.
+struct Guide {
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0));
+    float4 g2 = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(-1));
+};
+__device__ __forceinline__ void guide_of_hit(Guide& g, const LaunchConst& C, const float4* __restrict__ tri_shade,
+                                             const float* __restrict__ mat, int ntri, int nmat, int W, int i, int tc,
+                                             float kc, int s) {
+    if (tc < 0 || tc >= ntri) return;
+    const float4 sh = tri_shade[tc];
+    const int m = __float_as_int(sh.w);
+    const rtm_f3 d = camera_dir(C, W, i);
+    g.g0 = make_float4(sh.x, sh.y, sh.z, kc);
+    g.g1.x = C.position.x + d.x * kc;
+    g.g1.y = C.position.y + d.y * kc;
+    g.g1.z = C.position.z + d.z * kc;
+    g.g2.w = __int_as_float(m);
+    if (m >= 0 && m < nmat) {
+        const int type = (int)mat[kMatF * m];
+        if (type == 1 || type == 2) {
+            g.g1.w = __int_as_float(s);
+            g.g2.x = rtm_fmax(mat[kMatF * m + 1], 0.01f);
+            g.g2.y = rtm_fmax(mat[kMatF * m + 2], 0.01f);
+            g.g2.z = rtm_fmax(mat[kMatF * m + 3], 0.01f);
+        }
+    }
+}
+
+// rt_accum_guides of a lens accumulation: guides_kernel (rt_denoise.hip) with the first hit out of the centre-hit
+// buffer -- a lens record's k, tri are its last sample's -- and the count out of the state
+__global__ void __launch_bounds__(256) lens_guides_kernel(const float4* __restrict__ state,
+                                                          const float2* __restrict__ centre,
+                                                          const float4* __restrict__ tri_shade,
+                                                          const float* __restrict__ mat, int ntri, int nmat,
+                                                          unsigned nloc, int W, int row0, int row_step, int npix,
+                                                          const LaunchConst* __restrict__ lconst,
+                                                          float4* __restrict__ out) {
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nloc) return;
+    Guide g;
+    int i;
+    if (lens_tile_pixel(p, W, row0, row_step, npix, &i)) {
+        const float2 h = centre[p];
+        guide_of_hit(g, *lconst, tri_shade, mat, ntri, nmat, W, i, __float_as_int(h.y), h.x,
+                     __float_as_int(state[2 * (size_t)p + 1].w));
+    }
+    out[3 * (size_t)p + 0] = g.g0;
+    out[3 * (size_t)p + 1] = g.g1;
+    out[3 * (size_t)p + 2] = g.g2;
+}
+
 LensArgs lens_args(const LensOptions& q, const float cam[10], int64_t npix, int64_t first) {
     LensArgs L;
     L.jitter = q.jitter;
@@ -341,11 +468,11 @@ LaunchConst* lens_const(const float cam[10], const float* env, void* work, hipSt
     return lc;
 }
 
-}  // namespace
-
-hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float cam[10], int64_t npix, int64_t first,
-                                int64_t count, float4* state, const LensOptions& lens, const RadianceOptions& q,
-                                void* work, hipStream_t stream) {
+// the render loop over `count` jobs under mapping `map` (count: the most jobs a listed launch can have -- its grid and
+// its runs are sized for it, the kernel reads the length)
+hipError_t launch_lens_jobs(const DevScene& sc, int traversal, const float cam[10], int64_t npix, int64_t first,
+                            int64_t count, int map, LensJobs J, float4* state, const LensOptions& lens,
+                            const RadianceOptions& q, void* work, hipStream_t stream) {
     if (count <= 0) return hipSuccess;
     if (!state || !work) return hipErrorInvalidValue;
     const int trav = traversal == TRAV_REF ? TRAV_REF : TRAV_FAST;
@@ -353,8 +480,13 @@ hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float c
     const int block = radiance_fit(sc, trav, q.block, &s2);
     if (block == 0) return hipErrorInvalidValue;
     const size_t lds = stack_lds_bytes(s2, trav, block);
-    const void* fn = trav == TRAV_REF ? (const void*)lens_radiance_kernel<TRAV_REF>
-                                      : (const void*)lens_radiance_kernel<TRAV_FAST>;
+    const void* const fns[2][3] = {
+        {(const void*)lens_radiance_kernel<TRAV_FAST, kMapContig>, (const void*)lens_radiance_kernel<TRAV_FAST, kMapTile>,
+         (const void*)lens_radiance_kernel<TRAV_FAST, kMapListed>},
+        {(const void*)lens_radiance_kernel<TRAV_REF, kMapContig>, (const void*)lens_radiance_kernel<TRAV_REF, kMapTile>,
+         (const void*)lens_radiance_kernel<TRAV_REF, kMapListed>}};
+    if (map < kMapContig || map > kMapListed) return hipErrorInvalidValue;
+    const void* fn = fns[trav == TRAV_REF][map];
     hipError_t e = hipSuccess;
     const int64_t resident = resident_blocks(fn, block, lds, q.max_waves, &e);
     if (e != hipSuccess) return e;
@@ -374,8 +506,76 @@ hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float c
     // the shortcuts that rest on every sample sharing one ray: the degenerate lens only
     if (lens.jitter != 0.0f || lens.aperture != 0.0f) flags &= ~(kLensFixedPoint | kLensSunCache);
     float e3 = q.env[3], e4 = q.env[4];
-    void* args[] = {&s2, &L, &state, &un, &spp, &maxb, &e3, &e4, &flags, &chunk, &counter, &clc};
+    void* args[] = {&s2, &L, &state, &un, &spp, &maxb, &e3, &e4, &flags, &chunk, &counter, &clc, &J};
     return hipLaunchKernel(fn, dim3((unsigned)grid), dim3((unsigned)block), args, lds, stream);
+}
+
+LensJobs lens_jobs(const FrameParams& fp, const uint32_t* list, const uint32_t* count) {
+    LensJobs J{};
+    J.row0 = fp.row0;
+    J.row_step = fp.row_step;
+    J.nloc = (unsigned)fp.nloc;
+    J.list = list;
+    J.count = count;
+    return J;
+}
+
+// the camera ray's kernels run in blocks of 256 or, where the stack of one does not fit, the largest that does
+template <typename F>
+hipError_t launch_lens_centre_(F fn, const DevScene& s2, int block, size_t lds, const LaunchConst* lc,
+                               const FrameParams& fp, float2* centre, hipStream_t stream) {
+    hipLaunchKernelGGL(fn, dim3((unsigned)((fp.nloc + block - 1) / block)), dim3((unsigned)block), lds, stream, s2, lc,
+                       fp.width, fp.row0, fp.row_step, (int)fp.npix, (unsigned)fp.nloc, centre);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_lens_radiance(const DevScene& sc, int traversal, const float cam[10], int64_t npix, int64_t first,
+                                int64_t count, float4* state, const LensOptions& lens, const RadianceOptions& q,
+                                void* work, hipStream_t stream) {
+    return launch_lens_jobs(sc, traversal, cam, npix, first, count, kMapContig, LensJobs{}, state, lens, q, work, stream);
+}
+
+hipError_t launch_lens_accum_init(const FrameParams& fp, float4* state, hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    if (!state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lens_init_kernel, dim3((unsigned)((fp.nloc + 255) / 256)), dim3(256), 0, stream, state,
+                       (unsigned)fp.nloc, fp.width, fp.row0, fp.row_step, (int)fp.npix);
+    return hipGetLastError();
+}
+
+hipError_t launch_lens_accum(const DevScene& sc, int traversal, const FrameParams& fp, float4* state,
+                             const uint32_t* list, const uint32_t* count, const LensOptions& lens,
+                             const RadianceOptions& q, void* work, hipStream_t stream) {
+    if (list && !count) return hipErrorInvalidValue;
+    return launch_lens_jobs(sc, traversal, fp.cam, fp.npix, 0, fp.nloc, list ? kMapListed : kMapTile,
+                            lens_jobs(fp, list, count), state, lens, q, work, stream);
+}
+
+hipError_t launch_lens_centre(const DevScene& sc, int traversal, const FrameParams& fp, float2* centre, void* work,
+                              hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    if (!centre || !work) return hipErrorInvalidValue;
+    const int trav = traversal == TRAV_REF ? TRAV_REF : TRAV_FAST;
+    DevScene s2;
+    const int block = radiance_fit(sc, trav, 256, &s2);
+    if (block == 0) return hipErrorInvalidValue;
+    const size_t lds = stack_lds_bytes(s2, trav, block);
+    const LaunchConst* lc = lens_const(fp.cam, nullptr, work, stream);
+    return trav == TRAV_REF ? launch_lens_centre_(lens_centre_kernel<TRAV_REF>, s2, block, lds, lc, fp, centre, stream)
+                            : launch_lens_centre_(lens_centre_kernel<TRAV_FAST>, s2, block, lds, lc, fp, centre, stream);
+}
+
+hipError_t launch_lens_guides(const DevScene& sc, const FrameParams& fp, const float4* state, const float2* centre,
+                              void* work, float4* d_guides, hipStream_t stream) {
+    if (fp.nloc <= 0) return hipSuccess;
+    if (!state || !centre || !work || !d_guides) return hipErrorInvalidValue;
+    const LaunchConst* lc = lens_const(fp.cam, nullptr, work, stream);
+    hipLaunchKernelGGL(lens_guides_kernel, dim3((unsigned)((fp.nloc + 255) / 256)), dim3(256), 0, stream, state, centre,
+                       sc.tri_shade, sc.mat, sc.ntri, sc.nmat, (unsigned)fp.nloc, fp.width, fp.row0, fp.row_step,
+                       (int)fp.npix, lc, d_guides);
+    return hipGetLastError();
 }
 
 hipError_t launch_lens_rays(const float cam[10], int64_t npix, int64_t first, int64_t count, int sample0,

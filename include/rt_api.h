@@ -210,7 +210,8 @@ int rt_accum_add_selected_device(rt_ctx* ctx, int device_index, int spp, float* 
 
 /* Denoised previews: first-hit guide buffers out of the accumulation's state, and an edge-aware filter they
  * drive.  Nothing is rendered, no ray is traced and the state is untouched: rt_accum_read before and after
- * gives the same bits.
+ * gives the same bits.  (One exception to "no ray is traced": the first guides call of a lens accumulation traces
+ * the pixel-centre ray of every tile pixel once -- rt_accum_begin_lens, contract E3.)
  *
  * Guides: three float4 per pixel (12 floats), from the pixel's cached camera hit and its own sample count.
  *   G0 = (n.x, n.y, n.z, k)   n the normal the shading uses (the first vertex's, face[4]), k the hit distance;
@@ -430,6 +431,43 @@ int rt_lens_rays_device(rt_ctx* ctx, int device_index, const float cam[10], cons
                         int64_t first, int64_t count, int sample0, int nsamples, float* d_rays, void* stream);
 int rt_radiance_resolve_device(rt_ctx* ctx, int device_index, const rt_radiance_state* d_state, int64_t n,
                                float* d_rgb, void* stream);
+
+/* Progressive lens frames: an accumulation whose every sample goes down lens_ray(cam, lens, i, s) as above, so the
+ * frames that refine, adapt and denoise get anti-aliased edges and depth of field.
+ *   rt_accum_begin_lens         opens the context's one accumulation as rt_accum_begin does (replacing an open one),
+ *                               every slot holding its rows of the frame;
+ *   rt_accum_begin_lens_device  opens slot device_index's, of the rows row0, row0 + row_step, ..., as
+ *                               rt_accum_begin_device does.  The records are initialised on the slot's own stream;
+ *                               later launches on any stream are ordered after that as after any launch.
+ * Every other rt_accum_* entry point works on the open accumulation, whichever kind it is: add, add_rgb8, read,
+ * samples, end; mark, select, select_mask, select_all, selection, sample_map, add_selected; guides, denoise; and all
+ * _device forms.  The rules above carry over unchanged: what invalidates the accumulation; that a selected add needs
+ * a full add first; RT_ACCUM_MAX_SAMPLES; the tile forms enqueue on `stream` and never wait; buffers grow on first
+ * use.  Of the options, "block" and "radiance_grid" apply to a lens add (the engines are rt_lens_radiance's: REF, brute
+ * force, or the BVH2 walk with the whole stack in LDS); "slices", "pilot", "spec", "team", "walk_team" and "bvh_width"
+ * do not.  Padding pixels of a partial last row get no sample and no ray and are never selected.
+ * Contracts, bit for bit:
+ *   E1  Take any sequence of full and selected adds, on any engine, block, grid, tile or split over slots.  A pixel i
+ *       that has received n samples then holds the record that rt_lens_radiance returns for (cam, env, lens, npix,
+ *       first = i, count = 1, spp = n, max_bounce, flags = 0), in all 32 bytes.  The frame is
+ *       fmax(fmin(sum / (float)n, 1), 0) of those records.
+ *   E2  With jitter = 0 and aperture = 0 every frame, sample map, selection and guide equals the plain accumulation's
+ *       for the same arguments, and so the frame equals rt_render's.
+ *   E3  The guides of a lens accumulation equal, in all 12 floats, the guides of a plain accumulation of the same cam,
+ *       npix, scene and traversal whose pixels hold the same counts: the first hit is that of the pixel-centre pinhole
+ *       ray (genCameraRay(i): rt_camera_rays' ray, traced as rt_trace traces it), whatever the lens -- a lens record's
+ *       k, tri are its LAST sample's hit, not the pixel's.  The first guides call of a lens accumulation therefore
+ *       traces that one ray per tile pixel into a buffer of the slot (8 bytes per pixel; dropped by begin, end and
+ *       invalidation); later calls trace nothing.  The state is untouched either way: rt_accum_read before and after
+ *       gives the same bits.  With aperture > 0 the guides describe the geometry in focus at the pixel's centre, so
+ *       the filter under-smooths edges that are out of focus; no quality claim is made for that case.
+ * Errors: rt_accum_begin's argument and state checks, then a NULL lens, a jitter or aperture that is not finite or is
+ * negative, a focus that is not finite and > 0 (RT_ERR_ARG); RT_ERR_SCENE when the BVH2 stack does not fit a block of
+ * 64 lanes, as for rt_lens_radiance.  A failing begin leaves things as a failing rt_accum_begin leaves them. */
+int rt_accum_begin_lens(rt_ctx* ctx, const float cam[10], const float env[5], const rt_lens* lens, int64_t npix,
+                        int max_bounce);
+int rt_accum_begin_lens_device(rt_ctx* ctx, int device_index, const float cam[10], const float env[5],
+                               const rt_lens* lens, int64_t npix, int max_bounce, int row0, int row_step);
 
 /* Same traversal as the render, instrumented: accumulates
  * counts[0] = BVH node fetches, [1] = triangle tests, [2] = rays traced,

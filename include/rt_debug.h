@@ -266,6 +266,13 @@ int rt_debug_last_refill(int64_t out[3]);
 int rt_debug_brute_lean(const float* materialData, int64_t n_mat, const float env[5], const int32_t frame[7],
                         const int32_t kernel[6], int32_t out[2]);
 
+/* The state records of the open host accumulation (rt_accum_begin or rt_accum_begin_lens), one per frame pixel in the
+ * frame's order: every slot's tile-packed state read back and its rows gathered, as rt_accum_read gathers the frame.
+ * Blocking; nothing is rendered and the accumulation is untouched.  RT_ERR_STATE without an open, valid host
+ * accumulation.  A pixel that has no sample yet holds what its begin left there: a lens accumulation's initial record
+ * (sum 0, n 0, the frame's seeds), undefined words for a plain one. */
+int rt_debug_accum_state(rt_ctx* ctx, rt_radiance_state* out /* [npix], frame order */);
+
 #ifdef __cplusplus
 }
 #endif
