@@ -43,6 +43,19 @@ def _ibl_rgba(h_IBL) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+class History(object):
+    """What a frame knew when the camera moved (``Progressive.history``): the frame ``rgb`` float32 ``[3*imgDim]``,
+    its guides ``[imgDim, 12]`` -- whose ``f`` word is the history's length in samples -- and the camera ``cam``
+    they were made with; ``width`` is ``int(cam[6])``.  ``Progressive.reprojected`` of the next view takes it."""
+
+    def __init__(self, rgb: np.ndarray, guides: np.ndarray, cam: np.ndarray, imgDim: int):
+        self.rgb = rgb
+        self.guides = guides
+        self.cam = cam
+        self.imgDim = int(imgDim)
+        self.width = int(cam[6])
+
+
 class Progressive(object):
     """A frame that takes more samples (``KernelLauncher.begin_progressive``; rt_accum_* of rt_api.h).
 
@@ -51,10 +64,11 @@ class Progressive(object):
     ``begin_progressive_lens`` it is a lens frame instead: read ``lens_frame`` for ``launch_Raytracing`` below.
     """
 
-    def __init__(self, ctx: "_native.Context", imgDim: int):
+    def __init__(self, ctx: "_native.Context", imgDim: int, cam=None):
         self._ctx = ctx
         self._n = int(imgDim)
         self._open = True
+        self._cam = None if cam is None else np.array(cam, dtype=np.float32).reshape(-1)[:10]
 
     def _out(self, out, dtype):
         if not self._open:
@@ -187,6 +201,51 @@ class Progressive(object):
         out = self._out(out, np.float32)
         self._ctx.accum_denoise(_native.DenoiseParams(passes, normal_squarings, sigma_c, sigma_p), out=out.reshape(-1))
         return out
+
+    # -- temporal reprojection: carry the frame's history across a camera move.  Nothing is rendered and the
+    # accumulation is untouched: ``image()`` stays the exact frame. --
+    def history(self) -> History:
+        """The frame and the guides at the samples done, with the camera: what ``reprojected`` of the next view
+        takes.  Read it before the ``begin_progressive*`` that replaces this accumulation."""
+        self._live()
+        if self._cam is None:
+            raise RuntimeError("this progressive render was opened without its camera")
+        return History(self.image(), self._ctx.accum_guides(), self._cam.copy(), self._n)
+
+    def reprojected(self, history: History, sigma_p: float = 0.02, normal_min: float = 0.9, max_history: float = 64.0,
+                    min_weight: float = 0.25, denoise: bool = False, out: Optional[np.ndarray] = None,
+                    return_history: bool = False):
+        """The frame at the samples done, blended with ``history`` -- the frame of another camera on the same scene
+        and environment -- gathered into this view (rt_accum_reproject of rt_api.h): a pixel whose first hit the
+        previous view saw too keeps that view's samples, up to ``max_history`` of them.  With ``denoise`` the result
+        goes through the edge-aware filter, whose colour bandwidth follows the blended counts (``sigma_p`` is shared,
+        the other filter parameters are the defaults).  Pixels without history are ``image()``'s, bit for bit.  With
+        ``return_history`` returns ``(frame, History)``: the blended, unfiltered frame and its guides under this
+        camera, the history of the next move."""
+        self._live()
+        if not isinstance(history, History):
+            raise TypeError("history must be a History (Progressive.history)")
+        if history.imgDim != self._n:
+            raise ValueError(f"the history has {history.imgDim} pixels, this frame {self._n}")
+        sigma_p, normal_min = float(sigma_p), float(normal_min)
+        max_history, min_weight = float(max_history), float(min_weight)
+        for name, v in (("sigma_p", sigma_p), ("max_history", max_history)):
+            if not (v > 0.0 and v != float("inf")):
+                raise ValueError(f"{name} must be finite and > 0")
+        for name, v in (("normal_min", normal_min), ("min_weight", min_weight)):
+            if not (v == v and abs(v) != float("inf")):
+                raise ValueError(f"{name} must be finite")
+        if return_history and self._cam is None:
+            raise RuntimeError("this progressive render was opened without its camera")
+        out = self._out(out, np.float32)
+        rgb, guides = self._ctx.accum_reproject(history.rgb, history.guides, history.cam,
+                                                _native.ReprojectParams(sigma_p, normal_min, max_history, min_weight))
+        if denoise:
+            self._ctx.denoise(rgb, guides, self._n, history.width, _native.DenoiseParams(sigma_p=sigma_p),
+                              out=out.reshape(-1))
+        else:
+            out.reshape(-1)[:3 * self._n] = rgb
+        return (out, History(rgb, guides, self._cam.copy(), self._n)) if return_history else out
 
     @property
     def samples(self) -> int:
@@ -334,7 +393,7 @@ class KernelLauncher(object):
         if getattr(self, "_progressive", None) is not None:
             self._progressive._open = False   # replaced: the context holds one accumulation
         self._ctx.accum_begin(cam[:10], env[:5], imgDim, int(maxBounce))
-        self._progressive = Progressive(self._ctx, imgDim)
+        self._progressive = Progressive(self._ctx, imgDim, cam[:10])
         return self._progressive
 
     def begin_progressive_lens(self, h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_light_data,
@@ -361,7 +420,7 @@ class KernelLauncher(object):
         if getattr(self, "_progressive", None) is not None:
             self._progressive._open = False   # replaced: the context holds one accumulation
         self._ctx.accum_begin_lens(cam[:10], env[:5], lens, imgDim, int(maxBounce))
-        self._progressive = Progressive(self._ctx, imgDim)
+        self._progressive = Progressive(self._ctx, imgDim, cam[:10])
         return self._progressive
 
     def upload_scene(self, h_vertex_p, h_vertex_n, h_vertex_uv, h_face_data, h_material_data, h_BVH) -> None:

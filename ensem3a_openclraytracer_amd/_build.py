@@ -19,7 +19,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libensem3a_rt.so")
 OBJDIR = os.path.join(ROOT, "build", "native")
 
-SOURCES = ["rt_kernels.hip", "rt_accum.hip", "rt_adaptive.hip", "rt_denoise.hip", "rt_spec.hip", "rt_debug_fn.hip", "rt_query.hip", "rt_radiance.hip", "rt_lens.hip", "rt_api.hip", "scene_pack.cpp", "bvh_build.cpp", "bvh_sah.cpp", "obj_load.cpp"]
+SOURCES = ["rt_kernels.hip", "rt_accum.hip", "rt_adaptive.hip", "rt_denoise.hip", "rt_reproject.hip", "rt_spec.hip", "rt_debug_fn.hip", "rt_query.hip", "rt_radiance.hip", "rt_lens.hip", "rt_api.hip", "scene_pack.cpp", "bvh_build.cpp", "bvh_sah.cpp", "obj_load.cpp"]
 # -ffp-contract=off: the numerics contract (rtm.h) places every fused multiply-add explicitly.
 COMMON = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-Wall",
           "-Wno-unused-function", "-I", os.path.join(ROOT, "include")]

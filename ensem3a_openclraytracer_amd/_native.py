@@ -35,7 +35,8 @@ EXPORTED = (
     "rt_accum_mark", "rt_accum_select", "rt_accum_select_mask", "rt_accum_select_all", "rt_accum_selection",
     "rt_accum_sample_map", "rt_accum_add_selected", "rt_accum_mark_device", "rt_accum_select_device",
     "rt_accum_select_mask_device", "rt_accum_select_all_device", "rt_accum_add_selected_device",
-    "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise",
+    "rt_accum_guides", "rt_accum_guides_device", "rt_denoise_device", "rt_accum_denoise", "rt_denoise",
+    "rt_reproject_basis", "rt_reproject_device", "rt_accum_reproject",
     "rt_trace", "rt_trace_device",
     "rt_radiance", "rt_radiance_device", "rt_camera_rays", "rt_camera_rays_device",
     "rt_lens_radiance", "rt_lens_radiance_device", "rt_lens_rays", "rt_lens_rays_device", "rt_radiance_resolve_device",
@@ -54,7 +55,8 @@ EXPORTED = (
 # tools/sanitize.sh) compiles exactly these into an ASan/UBSan library that ENSEM3A_HOST_LIB selects.
 HOST_ONLY = ("rt_bvh_build", "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
              "rt_scene_check", "rt_scene_last_error", "rt_debug_quantise_axis", "rt_debug_brute_layout",
-             "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad")
+             "rt_debug_brute_clusters", "rt_debug_brute_shell", "rt_debug_brute_near", "rt_debug_brute_quad",
+             "rt_reproject_basis")
 
 _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -68,6 +70,16 @@ class DenoiseParams(ctypes.Structure):
 
     def __init__(self, passes: int = 5, normal_squarings: int = 5, sigma_c: float = 1.5, sigma_p: float = 0.02):
         super().__init__(int(passes), int(normal_squarings), float(sigma_c), float(sigma_p))
+
+
+class ReprojectParams(ctypes.Structure):
+    """rt_reproject_params of rt_api.h; the defaults are the library's."""
+    _fields_ = [("sigma_p", ctypes.c_float), ("normal_min", ctypes.c_float), ("max_history", ctypes.c_float),
+                ("min_weight", ctypes.c_float)]
+
+    def __init__(self, sigma_p: float = 0.02, normal_min: float = 0.9, max_history: float = 64.0,
+                 min_weight: float = 0.25):
+        super().__init__(float(sigma_p), float(normal_min), float(max_history), float(min_weight))
 
 
 GUIDE_FLOATS = 12   # three float4 per pixel: n | k, P | f, a | m (rt_api.h)
@@ -218,6 +230,11 @@ def lib():
             "rt_accum_guides_device": (_i32, [_c_p, _i32, _c_p, _c_p]),
             "rt_denoise_device": (_i32, [_c_p, _i32, _c_p, _c_p, _i64, _i32, ctypes.POINTER(DenoiseParams), _c_p, _c_p]),
             "rt_accum_denoise": (_i32, [_c_p, ctypes.POINTER(DenoiseParams), _c_p]),
+            "rt_denoise": (_i32, [_c_p, _c_p, _c_p, _i64, _i32, ctypes.POINTER(DenoiseParams), _c_p]),
+            "rt_reproject_basis": (_i32, [_c_p, _c_p]),
+            "rt_reproject_device": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _c_p, _c_p, _i64, _i32,
+                                           ctypes.POINTER(ReprojectParams), _c_p, _c_p, _c_p]),
+            "rt_accum_reproject": (_i32, [_c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ReprojectParams), _c_p, _c_p]),
             "rt_trace": (_i32, [_c_p, _c_p, _i64, _i32, _c_p]),
             "rt_trace_device": (_i32, [_c_p, _i32, _c_p, _i64, _i32, _c_p, _c_p]),
             "rt_radiance": (_i32, [_c_p, _c_p, _i64, _c_p, _i32, _i32, _i32, _c_p]),
@@ -320,6 +337,18 @@ def i32(a) -> np.ndarray:
 
 def ptr(a: np.ndarray):
     return a.ctypes.data if a is not None and a.size else None
+
+
+def reproject_basis(cam) -> np.ndarray:
+    """rt_reproject_basis: the 16 floats the reprojection kernel takes of a camera (host only, no GPU)."""
+    c = f32(cam).reshape(-1)
+    if c.size != 10:
+        raise ValueError("cam must have 10 floats")
+    out = np.zeros(16, np.float32)
+    st = host_lib().rt_reproject_basis(ptr(c), out.ctypes.data)
+    if st != 0:
+        raise NativeError(st, "rt_reproject_basis: cam must be finite")
+    return out
 
 
 def device_count() -> int:
@@ -600,6 +629,53 @@ class Context:
         self._check(lib().rt_accum_denoise(self.handle, ctypes.byref(params) if params is not None else None,
                                            out.ctypes.data))
         return out
+
+    def denoise(self, rgb, guides, npix: int, width: int, params: "DenoiseParams" = None,
+                out: np.ndarray = None) -> np.ndarray:
+        """rt_denoise: the filter on host arrays (float32 ``[3*npix]``, ``[12*npix]``), blocking."""
+        c, g = f32(rgb).reshape(-1), f32(guides).reshape(-1)
+        if c.size < 3 * int(npix) or g.size < GUIDE_FLOATS * int(npix):
+            raise ValueError("rgb needs 3*npix floats and guides 12*npix")
+        if out is None:
+            out = np.zeros(3 * int(npix), np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < 3 * int(npix):
+            raise ValueError("output must be a contiguous float32 array of 3*npix elements")
+        self._check(lib().rt_denoise(self.handle, ptr(c), ptr(g), int(npix), int(width),
+                                     ctypes.byref(params) if params is not None else None, out.ctypes.data))
+        return out
+
+    # -- temporal reprojection (rt_reproject_device / rt_accum_reproject) --
+    def reproject_device(self, d_prev_rgb_ptr: int, d_prev_guides_ptr: int, prev_cam, d_cur_rgb_ptr: int,
+                         d_cur_guides_ptr: int, npix: int, width: int, d_out_rgb_ptr: int, d_out_guides_ptr: int,
+                         params: "ReprojectParams" = None, stream_ptr: int = 0, device_index: int = 0) -> None:
+        """rt_reproject_device: frames and guides in device memory (``params`` None = the defaults); never waits."""
+        cam = f32(prev_cam).reshape(-1)
+        if cam.size != 10:
+            raise ValueError("prev_cam must have 10 floats")
+
+        def p(x):
+            return _c_p(int(x)) if x else None
+        self._check(lib().rt_reproject_device(self.handle, int(device_index), p(d_prev_rgb_ptr), p(d_prev_guides_ptr),
+                                              ptr(cam), p(d_cur_rgb_ptr), p(d_cur_guides_ptr), int(npix), int(width),
+                                              ctypes.byref(params) if params is not None else None,
+                                              p(d_out_rgb_ptr), p(d_out_guides_ptr), self._stream(stream_ptr)))
+
+    def accum_reproject(self, prev_rgb, prev_guides, prev_cam, params: "ReprojectParams" = None,
+                        out: np.ndarray = None):
+        """rt_accum_reproject: the previous frame and guides (host arrays of the open accumulation's size) gathered
+        into its view.  Returns ``(rgb float32[3*npix], guides float32[npix, 12])``; the state is untouched."""
+        n = getattr(self, "_accum_npix", 0)
+        c, g, cam = f32(prev_rgb).reshape(-1), f32(prev_guides).reshape(-1), f32(prev_cam).reshape(-1)
+        if cam.size != 10:
+            raise ValueError("prev_cam must have 10 floats")
+        if n and (c.size != 3 * n or g.size != GUIDE_FLOATS * n):
+            raise ValueError(f"the history must hold 3*{n} colour and 12*{n} guide floats, got {c.size} and {g.size}")
+        out = self._accum_out(out, np.float32)
+        out_g = np.zeros((max(n, 1), GUIDE_FLOATS), np.float32)
+        self._check(lib().rt_accum_reproject(self.handle, ptr(c), ptr(g), ptr(cam),
+                                             ctypes.byref(params) if params is not None else None, out.ctypes.data,
+                                             out_g.ctypes.data))
+        return out, out_g[:n]
 
     # -- ray queries (rt_trace / rt_trace_device) --
     def trace(self, rays8, mode: int = RT_QUERY_CLOSEST) -> np.ndarray:

@@ -103,6 +103,10 @@ struct Device {
     // filter's scratch (X twice, N, P: 64 bytes per frame pixel) and the launch constants of the guide kernel;
     // the host forms' guides of this slot's tile; and, on the slot that filters, the frame-shaped input and output
     DevBuf dn, dn_const, guides, dn_rgb, dn_guides, dn_out;
+    // Temporal reprojection's host form (rt_accum_reproject) and rt_denoise, on the slot that runs them, each
+    // allocated on first use: the caller's previous frame and guides, and the reprojected guides (the frame goes
+    // through dn_out)
+    DevBuf rp_rgb, rp_guides, rp_out_guides;
     // Ray queries (rt_trace*): the hand-out counter of the persistent kernels and, for the host form, this slot's
     // rays and results -- buffers of their own, allocated on first use
     DevBuf q_counter, q_rays, q_out;
@@ -1631,17 +1635,13 @@ int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const f
     return RT_OK;
 }
 
-int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb) {
-    int st = accum_host_readable(ctx, "rt_accum_denoise");
-    if (st) return st;
-    if (!out_rgb) return set_err(ctx, RT_ERR_ARG, "rt_accum_denoise: the output must not be NULL");
-    rt_denoise_params P;
-    st = denoise_params(ctx, params, &P);
-    if (st) return st;
+namespace {
+// The open host accumulation's frame and guides in frame order on slot 0 (the checks of accum_host_readable are the
+// caller's): every slot resolves the rows it holds; one slot: its tile is the frame, everything stays on the device;
+// several: the rows are assembled into frame-shaped buffers on slot 0, through the host.  Enqueued on slot 0's stream.
+int accum_frame_on_slot0(rt_ctx* ctx, const float** rgb_out, const float** guides_out) {
     const int nd = (int)ctx->devs.size();
     const int64_t npix = ctx->devs[0].acc_npix;
-    const int W = (int)ctx->devs[0].acc_cam[6];
-    // every slot resolves the frame and the guides of its rows
     for (int k = 0; k < nd; ++k) {
         Device& d = ctx->devs[k];
         HIP_OR_RET(ctx, hipSetDevice(d.id));
@@ -1652,17 +1652,15 @@ int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rg
             HIP_OR_RET(ctx, rt::launch_accum_resolve((const float4*)d.accum.p, (float*)d.out.p, d.acc_nloc, d.stream));
             HIP_OR_RET(ctx, mark_launch(d, d.stream));
         }
-        st = rt_accum_guides_device(ctx, k, (float*)d.guides.p, d.stream);
+        const int st = rt_accum_guides_device(ctx, k, (float*)d.guides.p, d.stream);
         if (st) return st;
     }
     Device& d0 = ctx->devs[0];
-    const float* rgb = (const float*)d0.out.p;   // one slot: its tile is the frame, everything stays on the device
-    const float* guides = (const float*)d0.guides.p;
-    std::vector<float> h_rgb, h_guides;          // (kept until the uploads are done)
-    if (nd > 1) {   // several slots: the rows assembled into frame-shaped buffers on slot 0, through the host
-        h_rgb.resize((size_t)npix * 3);
-        h_guides.resize((size_t)npix * 12);
-        st = accum_gather_host(ctx, h_rgb.data(), 3 * sizeof(float), [](Device& d) { return (const void*)d.out.p; });
+    *rgb_out = (const float*)d0.out.p;
+    *guides_out = (const float*)d0.guides.p;
+    if (nd > 1) {
+        std::vector<float> h_rgb((size_t)npix * 3), h_guides((size_t)npix * 12);   // (kept until the uploads are done)
+        int st = accum_gather_host(ctx, h_rgb.data(), 3 * sizeof(float), [](Device& d) { return (const void*)d.out.p; });
         if (st) return st;
         st = accum_gather_host(ctx, h_guides.data(), 12 * sizeof(float), [](Device& d) { return (const void*)d.guides.p; });
         if (st) return st;
@@ -1674,14 +1672,159 @@ int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rg
         HIP_OR_RET(ctx, hipMemcpyAsync(d0.dn_guides.p, h_guides.data(), h_guides.size() * sizeof(float), hipMemcpyHostToDevice,
                                        d0.stream));
         HIP_OR_RET(ctx, hipStreamSynchronize(d0.stream));
-        rgb = (const float*)d0.dn_rgb.p;
-        guides = (const float*)d0.dn_guides.p;
+        *rgb_out = (const float*)d0.dn_rgb.p;
+        *guides_out = (const float*)d0.dn_guides.p;
     }
+    return RT_OK;
+}
+}  // namespace
+
+int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb) {
+    int st = accum_host_readable(ctx, "rt_accum_denoise");
+    if (st) return st;
+    if (!out_rgb) return set_err(ctx, RT_ERR_ARG, "rt_accum_denoise: the output must not be NULL");
+    rt_denoise_params P;
+    st = denoise_params(ctx, params, &P);
+    if (st) return st;
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    const float *rgb, *guides;
+    st = accum_frame_on_slot0(ctx, &rgb, &guides);
+    if (st) return st;
+    Device& d0 = ctx->devs[0];
     HIP_OR_RET(ctx, hipSetDevice(d0.id));
     HIP_OR_RET(ctx, grow(d0, d0.dn_out, (size_t)npix * 3 * sizeof(float)));
     st = rt_denoise_device(ctx, 0, rgb, guides, npix, W, &P, (float*)d0.dn_out.p, d0.stream);
     if (st) return st;
     HIP_OR_RET(ctx, hipMemcpyAsync(out_rgb, d0.dn_out.p, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, d0.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d0.stream));
+    return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const float* rgb, const float* guides, int64_t npix, int width,
+               const rt_denoise_params* params, float* out_rgb) {
+    Device* dp = nullptr;
+    rt_denoise_params P;
+    int st = slot_of(ctx, 0, &dp);
+    if (!st) st = denoise_params(ctx, params, &P);
+    if (st) return st;
+    if (!rgb || !guides || !out_rgb) return set_err(ctx, RT_ERR_ARG, "rt_denoise: NULL buffer");
+    if (npix < 1 || npix > 0x7fffffff || width < 1)
+        return set_err(ctx, RT_ERR_ARG, "rt_denoise: bad frame (%lld pixels, rows of %d)", (long long)npix, width);
+    Device& d = *dp;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, grow(d, d.rp_rgb, (size_t)npix * 3 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.rp_guides, (size_t)npix * 12 * sizeof(float)));
+    HIP_OR_RET(ctx, grow(d, d.dn_out, (size_t)npix * 3 * sizeof(float)));
+    HIP_OR_RET(ctx, order_after_last(d, d.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(d.rp_rgb.p, rgb, (size_t)npix * 3 * sizeof(float), hipMemcpyHostToDevice, d.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(d.rp_guides.p, guides, (size_t)npix * 12 * sizeof(float), hipMemcpyHostToDevice, d.stream));
+    st = rt_denoise_device(ctx, 0, (const float*)d.rp_rgb.p, (const float*)d.rp_guides.p, npix, width, &P,
+                           (float*)d.dn_out.p, d.stream);
+    if (st) return st;
+    HIP_OR_RET(ctx, hipMemcpyAsync(out_rgb, d.dn_out.p, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+// ---- temporal reprojection: the previous frame and guides gathered into the current view ----
+namespace {
+int reproject_params(rt_ctx* ctx, const rt_reproject_params* in, rt::ReprojectParams* out) {
+    const rt_reproject_params defaults = {0.02f, 0.9f, 64.0f, 0.25f};
+    const rt_reproject_params p = in ? *in : defaults;
+    if (!(std::isfinite(p.sigma_p) && p.sigma_p > 0.0f) || !(std::isfinite(p.max_history) && p.max_history > 0.0f))
+        return set_err(ctx, RT_ERR_ARG, "reproject: sigma_p and max_history must be finite and > 0, got %g, %g",
+                       (double)p.sigma_p, (double)p.max_history);
+    if (!std::isfinite(p.normal_min) || !std::isfinite(p.min_weight))
+        return set_err(ctx, RT_ERR_ARG, "reproject: normal_min and min_weight must be finite, got %g, %g",
+                       (double)p.normal_min, (double)p.min_weight);
+    *out = rt::ReprojectParams{p.sigma_p, p.normal_min, p.max_history, p.min_weight};
+    return RT_OK;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+}  // namespace
+
+int rt_reproject_device(rt_ctx* ctx, int device_index, const float* d_prev_rgb, const float* d_prev_guides,
+                        const float prev_cam[10], const float* d_cur_rgb, const float* d_cur_guides, int64_t npix,
+                        int width, const rt_reproject_params* params, float* d_out_rgb, float* d_out_guides,
+                        void* stream) {
+    Device* dp = nullptr;
+    rt::ReprojectParams P;
+    int st = slot_of(ctx, device_index, &dp);
+    if (!st) st = reproject_params(ctx, params, &P);
+    if (st) return st;
+    if (!d_prev_rgb || !d_prev_guides || !prev_cam || !d_cur_rgb || !d_cur_guides || !d_out_rgb || !d_out_guides)
+        return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: NULL buffer");
+    if (npix < 1 || npix > 0x7fffffff || width < 1)
+        return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: bad frame (%lld pixels, rows of %d)", (long long)npix, width);
+    float basis[16];
+    if (rt_reproject_basis(prev_cam, basis) != RT_OK)
+        return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: prev_cam must be finite");
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(basis[k])) return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: prev_cam has no finite basis");
+    if ((int)prev_cam[6] != width)
+        return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: prev_cam's width %d is not the frame's %d", (int)prev_cam[6],
+                       width);
+    if (((uintptr_t)d_prev_guides & 15) || ((uintptr_t)d_cur_guides & 15) || ((uintptr_t)d_out_guides & 15))
+        return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: the guides must be 16-byte aligned");
+    const size_t nrgb = (size_t)npix * 3 * sizeof(float), ng = (size_t)npix * 12 * sizeof(float);
+    const struct { const void* p; size_t n; } ins[4] = {{d_prev_rgb, nrgb}, {d_prev_guides, ng}, {d_cur_rgb, nrgb},
+                                                         {d_cur_guides, ng}};
+    bool overlap = ranges_overlap(d_out_rgb, nrgb, d_out_guides, ng);
+    for (const auto& in : ins)
+        overlap = overlap || ranges_overlap(d_out_rgb, nrgb, in.p, in.n) || ranges_overlap(d_out_guides, ng, in.p, in.n);
+    if (overlap) return set_err(ctx, RT_ERR_ARG, "rt_reproject_device: the outputs overlap an input or each other");
+    rt::ReprojectBasis B;
+    std::memcpy(B.m, basis, sizeof(B.m));
+    std::memcpy(B.pos, basis + 9, sizeof(B.pos));
+    B.f = basis[12];
+    B.cam6 = basis[13];
+    Device& d = *dp;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    HIP_OR_RET(ctx, order_after_last(d, s));
+    HIP_OR_RET(ctx, rt::launch_reproject(d_prev_rgb, (const float4*)d_prev_guides, d_cur_rgb, (const float4*)d_cur_guides,
+                                         npix, width, B, P, d_out_rgb, (float4*)d_out_guides, s));
+    HIP_OR_RET(ctx, mark_launch(d, s));
+    return RT_OK;
+}
+
+int rt_accum_reproject(rt_ctx* ctx, const float* prev_rgb, const float* prev_guides, const float prev_cam[10],
+                       const rt_reproject_params* params, float* out_rgb, float* out_guides) {
+    int st = accum_host_readable(ctx, "rt_accum_reproject");
+    if (st) return st;
+    if (!prev_rgb || !prev_guides || !prev_cam || !out_rgb || !out_guides)
+        return set_err(ctx, RT_ERR_ARG, "rt_accum_reproject: NULL buffer");
+    rt::ReprojectParams P;
+    st = reproject_params(ctx, params, &P);
+    if (st) return st;
+    const int64_t npix = ctx->devs[0].acc_npix;
+    const int W = (int)ctx->devs[0].acc_cam[6];
+    float basis[16];
+    if (rt_reproject_basis(prev_cam, basis) != RT_OK || (int)prev_cam[6] != W)   // (before anything is enqueued)
+        return set_err(ctx, RT_ERR_ARG, "rt_accum_reproject: prev_cam must be finite and of the accumulation's width %d", W);
+    const float *rgb, *guides;
+    st = accum_frame_on_slot0(ctx, &rgb, &guides);
+    if (st) return st;
+    Device& d0 = ctx->devs[0];
+    const size_t nrgb = (size_t)npix * 3 * sizeof(float), ng = (size_t)npix * 12 * sizeof(float);
+    HIP_OR_RET(ctx, hipSetDevice(d0.id));
+    HIP_OR_RET(ctx, grow(d0, d0.rp_rgb, nrgb));
+    HIP_OR_RET(ctx, grow(d0, d0.rp_guides, ng));
+    HIP_OR_RET(ctx, grow(d0, d0.dn_out, nrgb));
+    HIP_OR_RET(ctx, grow(d0, d0.rp_out_guides, ng));
+    HIP_OR_RET(ctx, order_after_last(d0, d0.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(d0.rp_rgb.p, prev_rgb, nrgb, hipMemcpyHostToDevice, d0.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(d0.rp_guides.p, prev_guides, ng, hipMemcpyHostToDevice, d0.stream));
+    st = rt_reproject_device(ctx, 0, (const float*)d0.rp_rgb.p, (const float*)d0.rp_guides.p, prev_cam, rgb, guides, npix, W,
+                             params, (float*)d0.dn_out.p, (float*)d0.rp_out_guides.p, d0.stream);
+    if (st) return st;
+    HIP_OR_RET(ctx, hipMemcpyAsync(out_rgb, d0.dn_out.p, nrgb, hipMemcpyDeviceToHost, d0.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(out_guides, d0.rp_out_guides.p, ng, hipMemcpyDeviceToHost, d0.stream));
     HIP_OR_RET(ctx, hipStreamSynchronize(d0.stream));
     return RT_OK;
 }

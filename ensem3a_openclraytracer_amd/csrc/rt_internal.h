@@ -263,6 +263,15 @@ size_t denoise_scratch_bytes(int64_t npix);
 hipError_t launch_denoise(const float* d_rgb, const float4* d_guides, int64_t npix, int width, int passes, int nsq,
                           float sigma_c, float sigma_p, bool lds, float4* scratch, float* d_out,
                           hipStream_t stream);
+// Temporal reprojection (rt_reproject_device; the kernel in rt_reproject.hip's translation unit): the previous
+// frame and guides gathered into the current view, rt_api.h's definition.  basis: rt_reproject_basis' 16 floats less
+// the padding; npix > 0 pixels in rows of `width`; guides 16-byte aligned; the outputs overlap nothing.
+struct ReprojectBasis { float m[9]; float pos[3]; float f, cam6; };
+struct ReprojectParams { float sigma_p, normal_min, max_history, min_weight; };
+hipError_t launch_reproject(const float* d_prev_rgb, const float4* d_prev_guides, const float* d_cur_rgb,
+                            const float4* d_cur_guides, int64_t npix, int width, const ReprojectBasis& basis,
+                            const ReprojectParams& params, float* d_out_rgb, float4* d_out_guides,
+                            hipStream_t stream);
 // out[3 p ..] = clamp(acc / s) of the n pixels of an accumulation state (rt_accum_read)
 hipError_t launch_accum_resolve(const float4* state, float* d_out, int64_t n, hipStream_t stream);
 hipError_t launch_prep_frames(const DevScene& sc, float4* frame, hipStream_t stream);

@@ -23,6 +23,7 @@
 #include "../../include/rt_debug.h"
 #include "../../include/rt_scene.h"
 #include "bvh_sah.h"
+#include "rtm.h"
 
 using rt::HostScene;
 
@@ -1364,5 +1365,32 @@ extern "C" int rt_debug_brute_quad(const float* vp, int64_t nvp, const float* vn
                 std::memcpy(recs + 18 * f + 9 * j, hs.brute.data() + 16 * (size_t)q + 6, 9 * sizeof(float));
         }
     }
+    return RT_OK;
+}
+
+// rt_reproject_basis (rt_api.h): the previous camera as the reprojection kernel takes it -- genCameraRay's three
+// rotations undone on the unit vectors, the position, the focal length as make_const (rt_device.h) has it, the width.
+// Host only: rtm.h gives the bits the launch constants have.
+extern "C" int rt_reproject_basis(const float cam[10], float basis[16]) {
+    if (!cam || !basis) return RT_ERR_ARG;
+    for (int k = 0; k < 10; ++k)
+        if (!std::isfinite(cam[k])) return RT_ERR_ARG;
+    for (int j = 0; j < 3; ++j) {
+        rtm_f3 e = rtm_v3(j == 0 ? 1.0f : 0.0f, j == 1 ? 1.0f : 0.0f, j == 2 ? 1.0f : 0.0f);
+        e = rtm_rotate(-(cam[5] * (3.14f / 180.0f)), rtm_v3(0, 0, 1), e);
+        e = rtm_rotate(-(cam[4] * (3.14f / 180.0f)), rtm_v3(0, 1, 0), e);
+        e = rtm_rotate(-(cam[3] * (3.14f / 180.0f)), rtm_v3(1, 0, 0), e);
+        basis[j] = e.x;
+        basis[3 + j] = e.y;
+        basis[6 + j] = e.z;
+    }
+    basis[9] = cam[0];
+    basis[10] = cam[1];
+    basis[11] = cam[2];
+    const float focal_y = cam[1] - (1.0f / (2.0f * rtm_tan(cam[9] / 2.0f)));
+    basis[12] = cam[1] - focal_y;
+    basis[13] = cam[6];
+    basis[14] = 0.0f;
+    basis[15] = 0.0f;
     return RT_OK;
 }

@@ -268,6 +268,78 @@ int rt_accum_guides_device(rt_ctx* ctx, int device_index, float* d_guides, void*
 int rt_denoise_device(rt_ctx* ctx, int device_index, const float* d_rgb, const float* d_guides, int64_t npix,
                       int width, const rt_denoise_params* params, float* d_out, void* stream);
 int rt_accum_denoise(rt_ctx* ctx, const rt_denoise_params* params, float* out_rgb);
+/* rt_denoise: rt_denoise_device on HOST arrays rgb[3 * npix], guides[12 * npix] -> out_rgb[3 * npix], blocking
+ * (slot 0): the filter for a frame that is not the accumulation's own, such as rt_accum_reproject's.  Errors as
+ * rt_denoise_device. */
+int rt_denoise(rt_ctx* ctx, const float* rgb, const float* guides, int64_t npix, int width,
+               const rt_denoise_params* params, float* out_rgb);
+
+/* Temporal reprojection: carry a frame's history across a camera move.  The previous view's frame and guides are
+ * gathered into the current view -- G1 is every pixel's world-space first hit, G0 and G2 say whether two pixels see
+ * the same surface -- and blended with the current frame by sample counts.  One image-space kernel: no ray is
+ * traced and no accumulation state is touched, so rt_accum_read stays the exact frame.  Scene and environment must
+ * be what they were when the history was made: that is the caller's job, nothing here can check it.
+ *
+ * The history length lives in the guides' f word: in prev_guides f > 0 means "filterable, with this many samples'
+ * worth of history"; out_guides is cur_guides with f raised to the blended count.  out_guides therefore goes
+ * straight into rt_denoise_device, whose colour bandwidth narrows accordingly, and it is the prev_guides of the
+ * next move: frames chain without a side buffer.
+ *
+ * rt_reproject_basis (host only, no GPU call): the previous camera as the 16 floats the kernel takes.
+ *   basis[0..8]   M, row-major: column j is the unit vector e_j taken through rtm_rotate about z by
+ *                 -(cam[5] * (3.14f / 180.0f)), then about y by -(cam[4] * ...), then about x by -(cam[3] * ...):
+ *                 genCameraRay's three rotations (Raytracing.cl:18-37) undone, in reverse order;
+ *   basis[9..11]  cam[0..2], the position;
+ *   basis[12]     cam[1] - focal.y with focal.y = cam[1] - 1.0f / (2.0f * tan(cam[9] / 2.0f)) as the frame's launch
+ *                 constants have it: the focal length f;
+ *   basis[13]     cam[6];  basis[14..15] = 0.
+ * RT_ERR_ARG: a NULL pointer or a cam that is not finite.
+ *
+ * Definition, per pixel p < npix -- everything is fp32, evaluated in the order written, without contraction;
+ * W = width, H = ceil(npix / W), the guides split as above (n, k | P, f | a, m), min(x, y) = x < y ? x : y:
+ *   0. f_p <= 0 (a miss, an emitter, glass): no history.
+ *   1. v = P_p - pos;  l.x = (M00 * v.x + M01 * v.y) + M02 * v.z, l.y and l.z likewise from rows 1 and 2.
+ *      !(l.y > 0): no history.
+ *   2. t = f / l.y;  u = (l.x * t + 0.5f) * cam6;  vv = (0.5f - l.z * t) * cam6 -- the continuous pixelY (column)
+ *      and pixelX (row) of genCameraRay.  !(u >= -1 && u < (float)W && vv >= -1 && vv < (float)H): no history
+ *      (a NaN fails it).  c0 = floorf(u), r0 = floorf(vv), fu = u - c0, fv = vv - r0.
+ *   3. acc = 0, ws = 0, hs = 0.  Four taps (dr, dc) = (0,0), (0,1), (1,0), (1,1) in that order: c = (int)c0 + dc,
+ *      r = (int)r0 + dr, b = (dc ? fu : 1 - fu) * (dr ? fv : 1 - fv), and the tap's pixel index is
+ *          q = (r + 1) * W + c - 1,
+ *      the inverse of genCameraRay's pixelY = (i + 1) % W, pixelX = (i - pixelY) / W, exact for every i >= W - 1
+ *      (indices 0 .. W - 2 duplicate row 0 and are never taps).  A tap is valid iff 0 <= c < W, r >= 0, q < npix,
+ *      f_q > 0, m_q == m_p, (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_min, and with d = P_q - P_p
+ *      |(n_p.x * d.x + n_p.y * d.y) + n_p.z * d.z| <= sigma_p * k_p  (n, k, P, f, m of q from prev_guides).
+ *      A valid tap adds: acc += b * (prev_rgb_q / a_q) per channel (divide, multiply, then add); ws += b;
+ *      hs += b * (float)f_q.
+ *   4. !(ws >= min_weight && ws > 0): no history.  Else hx = acc / ws, h = min(hs / ws, max_history).
+ *   5. x_p = cur_rgb_p / a_p;  s = (float)f_p;  tot = h + s;  x = (hx * h + x_p * s) / tot per channel;
+ *      out_rgb_p = max(min(x * a_p, 1), 0) (rtm.h's fmin, fmax: a NaN goes to 1);  out_guides_p = cur_guides_p
+ *      with f = (int)tot, or 2147483647 when !(tot < 2^31).
+ *   6. "No history" anywhere above: out_rgb_p and out_guides_p are the current inputs, copied bit for bit.
+ * The defaults (a NULL params): sigma_p = 0.02f, the filter's plane tolerance with the same meaning;
+ * normal_min = 0.9f; max_history = 64; min_weight = 0.25f.
+ *
+ *   rt_reproject_device  whole frames in DEVICE memory on slot device_index, independent of the accumulation:
+ *                        rgb arrays of 3 * npix floats, guide arrays of 12 * npix floats, 16-byte aligned, in frame
+ *                        order.  The outputs may overlap neither an input nor each other; d_prev_* may be d_cur_*.
+ *                        The basis is evaluated on the host by rt_reproject_basis and passed to the kernel by value.
+ *                        Enqueues on `stream` and never waits.
+ *   rt_accum_reproject   host form on the open accumulation, plain or lens: resolves its frame and guides on every
+ *                        slot, reprojects the HOST arrays prev_rgb[3 * npix], prev_guides[12 * npix] into it on slot
+ *                        0 and reads out_rgb[3 * npix] and out_guides[12 * npix] back, blocking.  The width is the
+ *                        accumulation's.  Errors as rt_accum_read; the state is untouched.
+ * RT_ERR_ARG: NULL buffers, npix < 1, npix >= 2^31, width < 1, (int)prev_cam[6] != width, a prev_cam that is not
+ * finite (or whose basis is not), sigma_p or max_history not finite and > 0, normal_min or min_weight not finite,
+ * misaligned guides, outputs that overlap.  Nothing is enqueued and no output is written. */
+typedef struct { float sigma_p, normal_min, max_history, min_weight; } rt_reproject_params; /* 16 bytes */
+int rt_reproject_basis(const float cam[10], float basis[16]);
+int rt_reproject_device(rt_ctx* ctx, int device_index, const float* d_prev_rgb, const float* d_prev_guides,
+                        const float prev_cam[10], const float* d_cur_rgb, const float* d_cur_guides, int64_t npix,
+                        int width, const rt_reproject_params* params, float* d_out_rgb, float* d_out_guides,
+                        void* stream);
+int rt_accum_reproject(rt_ctx* ctx, const float* prev_rgb, const float* prev_guides, const float prev_cam[10],
+                       const rt_reproject_params* params, float* out_rgb, float* out_guides);
 
 /* Ray queries: closest-hit and any-hit batches of the caller's own rays through the uploaded scene (no
  * counterpart in the reference).  Picking off the pixel grid, visibility between two points, ambient-occlusion or
