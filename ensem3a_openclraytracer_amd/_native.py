@@ -24,6 +24,8 @@ RT_BVH_SAH = 1
 RT_ERR_ARG = 1
 RT_ERR_STATE = 3
 RT_ACCUM_MAX_SAMPLES = 1 << 24   # rt_api.h: the most samples per pixel an accumulation may reach
+SPEC_PICK = 10   # rt_debug.h RT_SPEC_PICK (rt_internal.h kSpecPick): a pass-2 pick word above it means trails
+PILOT_FIELDS = ("two_pass", "nloc", "pilot", "chunk", "levels", "lanes", "left", "pick")   # rt_debug_last_pilot
 
 # Every symbol of include/rt_api.h and include/rt_debug.h (checked by tests).
 EXPORTED = (
@@ -48,6 +50,7 @@ EXPORTED = (
     "rt_debug_brute_slices",
     "rt_debug_last_slices",
     "rt_debug_brute_refill", "rt_debug_last_refill", "rt_debug_last_launch", "rt_debug_brute_lean",
+    "rt_debug_pilot_order", "rt_debug_pilot_pick", "rt_debug_last_pilot",
     "rt_obj_parse", "rt_obj_size", "rt_obj_copy", "rt_obj_free", "rt_obj_last_error",
     "rt_scene_check", "rt_scene_last_error",
 )
@@ -274,6 +277,9 @@ def lib():
             "rt_debug_brute_refill": (_i32, [_i64, _i64, _i32, _c_p]),
             "rt_debug_last_refill": (_i32, [_c_p]),
             "rt_debug_last_launch": (_i32, [_c_p]),
+            "rt_debug_pilot_order": (_i32, [_c_p, _c_p, _i64, _i32, _i32, _i32, _i32, _c_p]),
+            "rt_debug_pilot_pick": (_i32, [_c_p, _c_p, _i64, _i64, _i32, _c_p]),
+            "rt_debug_last_pilot": (_i32, [_c_p, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_math": (_i32, [_c_p, _i32, _c_p, _c_p, _c_p, _i64]),
             "rt_debug_fn": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
             "rt_debug_trace": (_i32, [_c_p, _i32, _c_p, _c_p, _i64]),
@@ -894,6 +900,35 @@ class Context:
         self._check(lib().rt_debug_scene_info(self.handle, out.ctypes.data))
         return dict(fast_ok=bool(out[0]), depth=int(out[1]), nodes=int(out[2]), tris=int(out[3]),
                     brute_records=int(out[4]), brute_boxes=int(out[5]), wdq_omax=int(out[6]) * 1e-6)
+
+    def debug_pilot_order(self, cost, chunk: int, levels: int, pilot: int, max_bounce: int) -> np.ndarray:
+        """rt_debug_pilot_order: the pass-2 pixel order (uint32[n]) the device computes from ``cost`` (uint32[n]) with
+        the launches of a two-pass render.  Raises NativeError for arguments the entry point rejects."""
+        c = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+        out = np.zeros(max(c.size, 1), np.uint32)
+        self._check(lib().rt_debug_pilot_order(self.handle, c.ctypes.data, c.size, int(chunk), int(levels),
+                                               int(pilot), int(max_bounce), out.ctypes.data))
+        return out[: c.size]
+
+    def debug_pilot_pick(self, cost, lanes: int, spec: int):
+        """rt_debug_pilot_pick: ``(left, pick word)`` the device computes from ``cost`` (uint32[n]) for ``lanes``
+        resident lanes; the word is 1, 2 or 4 lanes per pixel, or ``SPEC_PICK`` + trails."""
+        c = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+        out = np.zeros(2, np.int32)
+        self._check(lib().rt_debug_pilot_pick(self.handle, c.ctypes.data, c.size, int(lanes), int(spec),
+                                              out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def debug_last_pilot(self):
+        """rt_debug_last_pilot: ``(info, cost, order)`` of the context's last render launch, which ran two passes
+        (NativeError with status RT_ERR_STATE when it ran one): info by name (``PILOT_FIELDS``), and the costs pass 1
+        wrote and the pass-2 order, uint32[nloc] each."""
+        info = np.zeros(len(PILOT_FIELDS), np.int64)
+        self._check(lib().rt_debug_last_pilot(self.handle, info.ctypes.data, None, None, 0))
+        n = int(info[1])
+        cost, order = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._check(lib().rt_debug_last_pilot(self.handle, info.ctypes.data, cost.ctypes.data, order.ctypes.data, n))
+        return {name: int(v) for name, v in zip(PILOT_FIELDS, info)}, cost, order
 
     def timings(self) -> dict:
         """Host wall times (ms) of the last set_scene (pack / upload), set_env and render (rt_debug_timings)."""

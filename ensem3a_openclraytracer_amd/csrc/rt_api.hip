@@ -71,6 +71,7 @@ struct Device {
     DevBuf stack_ovf;             // FAST traversal stack entries beyond the LDS part
     DevBuf nodes, wnodes, wleaves, tri_fast, brute, brute_box, brute_cbox, brute_crow, bvh9, tri_geo, tri_shade, tri_frame, mat, ibl, ibl_sum, out, out8, counts, work, scratch_a, scratch_b;
     DevBuf pilot;                 // two-pass launches: per-pixel state, cost and order (FrameParams::pilot_*)
+    rt::PilotNote pilot_note;     // ... and what the slot's last render launch did with it (rt_debug_last_pilot)
     DevBuf spec;                  // speculation: the trails' sample logs (FrameParams::spec_log)
     DevBuf slice;                 // sample slices: per-pixel state + samples done (FrameParams::slice_*)
     // Progressive accumulation of this slot's tile (rt_accum_*): the per-pixel state in a buffer of its own
@@ -710,22 +711,18 @@ hipError_t setup_pilot(rt_ctx* ctx, Device& d, rt::FrameParams& fp) {
         k = fp.spp / 8;
     }
     if (k >= fp.spp) return hipSuccess;
-    const size_t n = (size_t)fp.nloc;
-    // state 32 B | cost 4 B | order 4 B per pixel, bin totals + offsets (2 x 256), the chunk costs +
-    // chunk order (at most one chunk per pixel), the sort's segment histograms (256 per 256 chunks) and
-    // each pixel's pass-1 RNG offset (4 B, pilot_draws)
-    const size_t need = n * 40 + 2 * 256 * sizeof(uint32_t) + 2 * (n + 1) * sizeof(uint32_t) +
-                        (n + 256) * sizeof(uint32_t) + n * sizeof(uint32_t);
-    hipError_t e = grow(d, d.pilot, need);
+    // the state, cost and order of every pixel, the sort's scratch and the RNG offsets (rt_internal.h pilot_layout)
+    const rt::PilotLayout L = rt::pilot_layout((size_t)fp.nloc);
+    hipError_t e = grow(d, d.pilot, L.need);
     if (e != hipSuccess) return e;
     char* base = (char*)d.pilot.p;
     fp.pilot = k;
     fp.pilot_chunk = ctx->pilot_chunk > 0 ? ctx->pilot_chunk : (ctx->hs.nbrute > 0 ? 64 : 1);
     fp.pilot_levels = ctx->pilot_levels > 0 ? ctx->pilot_levels : 256;
     fp.pilot_state = (float4*)base;
-    fp.pilot_cost = (uint32_t*)(base + n * 32);
-    fp.pilot_order = (const uint32_t*)(base + n * 36);
-    fp.pilot_draws = (uint32_t*)(base + need - n * sizeof(uint32_t));
+    fp.pilot_cost = (uint32_t*)(base + L.cost);
+    fp.pilot_order = (const uint32_t*)(base + L.order);
+    fp.pilot_draws = (uint32_t*)(base + L.draws);
     // speculation (option "spec"): small tiles of the BVH2 walk continue as trails in pass 2
     const int64_t lanes = (int64_t)std::max(d.cus, 1) * rt::kWalkLanesPerCu;
     // up to 4 pixels per resident lane: pass 1 finishes the pixels that draw nothing (sky), and the device
@@ -826,7 +823,7 @@ int rt_render_device(rt_ctx* ctx, int device_index, const float cam[10], const f
     HIP_OR_RET(ctx, setup_pilot(ctx, d, fp));
     HIP_OR_RET(ctx, setup_slices(ctx, d, fp, s));
     HIP_OR_RET(ctx, rt::launch_render(dev_scene(ctx, d), fp, effective_traversal(ctx), ctx->block, d_out, nullptr,
-                                      (unsigned int*)d.work.p, s));
+                                      (unsigned int*)d.work.p, s, nullptr, &d.pilot_note));
     HIP_OR_RET(ctx, mark_launch(d, s));
     return RT_OK;
 }
@@ -937,7 +934,8 @@ int render_host_(rt_ctx* ctx, const float cam[10], const float env[5], int64_t n
         if (!d.host_pick) HIP_OR_RET(ctx, hipHostMalloc((void**)&d.host_pick, sizeof(int), hipHostMallocDefault));
         pend[k].host_pick = d.host_pick;
         HIP_OR_RET(ctx, rt::launch_render(dev_scene(ctx, d), fp, effective_traversal(ctx), ctx->block,
-                                          (float*)d.out.p, nullptr, (unsigned int*)d.work.p, d.stream, &pend[k]));
+                                          (float*)d.out.p, nullptr, (unsigned int*)d.work.p, d.stream, &pend[k],
+                                          &d.pilot_note));
         HIP_OR_RET(ctx, mark_launch(d, d.stream));   // (again after pass 2 below; an error in between leaves it ordered)
     }
     for (int k = 0; k < nd; ++k) {
@@ -1891,7 +1889,8 @@ int count_all(rt_ctx* ctx, const float cam[10], const float env[5], int64_t npix
     // counts are those of its unsliced frame)
     if (ctx->hs.nbrute > 0) HIP_OR_RET(ctx, setup_slices(ctx, d, fp, d.stream));
     HIP_OR_RET(ctx, rt::launch_render(dev_scene(ctx, d), fp, effective_traversal(ctx), ctx->block, (float*)d.out.p,
-                                      (unsigned long long*)d.counts.p, (unsigned int*)d.work.p, d.stream));
+                                      (unsigned long long*)d.counts.p, (unsigned int*)d.work.p, d.stream, nullptr,
+                                      &d.pilot_note));
     HIP_OR_RET(ctx, mark_launch(d, d.stream));
     HIP_OR_RET(ctx, hipMemcpyAsync(h, d.counts.p, sizeof h, hipMemcpyDeviceToHost, d.stream));
     HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
@@ -2468,6 +2467,84 @@ int rt_debug_last_launch(int32_t out[21]) {
                            k.ts,   k.acc,   n.team, n.walk_team,  n.slices, n.refill, n.grid, (int64_t)n.lds,
                            n.shell, n.near, n.quad, n.primary};
     for (int i = 0; i < 21; ++i) out[i] = (int32_t)std::min<int64_t>(v[i], INT32_MAX);
+    return RT_OK;
+}
+
+static_assert(RT_SPEC_PICK == rt::kSpecPick, "rt_debug.h states the pick word's trail code");
+
+int rt_debug_pilot_order(rt_ctx* ctx, const uint32_t* cost, int64_t n, int chunk, int levels, int pilot, int max_bounce,
+                         uint32_t* order_out) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!cost || !order_out) return set_err(ctx, RT_ERR_ARG, "rt_debug_pilot_order: cost and order_out must not be NULL");
+    // (the ranges of the options "pilot_chunk", "pilot_levels" and "pilot" and of a frame's maxBounce)
+    if (n <= 0 || n > INT32_MAX || chunk < 1 || chunk > 4096 || levels < 2 || levels > 256 || pilot < 1 ||
+        pilot > (1 << 20) || max_bounce > 4096)
+        return set_err(ctx, RT_ERR_ARG, "rt_debug_pilot_order: n %lld, chunk %d, levels %d, pilot %d, maxBounce %d",
+                       (long long)n, chunk, levels, pilot, max_bounce);
+    Device& d = ctx->devs[0];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    // scratch_a: a two-pass launch's scratch for a tile of n pixels, the cost and the order where it has them
+    const rt::PilotLayout L = rt::pilot_layout((size_t)n);
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, L.need));
+    uint32_t* dcost = (uint32_t*)((char*)d.scratch_a.p + L.cost);
+    uint32_t* dorder = (uint32_t*)((char*)d.scratch_a.p + L.order);
+    const size_t bytes = (size_t)n * sizeof(uint32_t);
+    HIP_OR_RET(ctx, hipMemcpyAsync(dcost, cost, bytes, hipMemcpyHostToDevice, d.stream));
+    HIP_OR_RET(ctx, rt::launch_pilot_order(dcost, n, chunk, levels, pilot, max_bounce, dorder, d.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(order_out, dorder, bytes, hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_debug_pilot_pick(rt_ctx* ctx, const uint32_t* cost, int64_t n, int64_t lanes, int spec, int32_t out[2]) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!cost || !out || n <= 0 || n > INT32_MAX || lanes < 1 || lanes > ((int64_t)1 << 40) || spec < 0 || spec > 1)
+        return set_err(ctx, RT_ERR_ARG, "rt_debug_pilot_pick: n %lld, lanes %lld, spec %d", (long long)n,
+                       (long long)lanes, spec);
+    Device& d = ctx->devs[0];
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    const size_t bytes = (size_t)n * sizeof(uint32_t);
+    HIP_OR_RET(ctx, grow(d, d.scratch_a, bytes));
+    HIP_OR_RET(ctx, grow(d, d.scratch_b, 2 * sizeof(int32_t)));
+    unsigned* left = (unsigned*)d.scratch_b.p;
+    HIP_OR_RET(ctx, hipMemcpyAsync(d.scratch_a.p, cost, bytes, hipMemcpyHostToDevice, d.stream));
+    HIP_OR_RET(ctx, rt::launch_pilot_pick((const uint32_t*)d.scratch_a.p, n, lanes, spec, left, (int*)(left + 1), d.stream));
+    HIP_OR_RET(ctx, hipMemcpyAsync(out, left, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
+int rt_debug_last_pilot(rt_ctx* ctx, int64_t info[8], uint32_t* cost_out, uint32_t* order_out, int64_t cap) {
+    if (!ctx) return set_err(nullptr, RT_ERR_ARG, "null context");
+    if (!info || cap < 0 || (cap > 0 && (!cost_out || !order_out)))
+        return set_err(ctx, RT_ERR_ARG, "rt_debug_last_pilot: bad arguments");
+    if (ctx->devs.size() != 1) return set_err(ctx, RT_ERR_ARG, "rt_debug_last_pilot: a single-device context only");
+    Device& d = ctx->devs[0];
+    const rt::PilotNote& note = d.pilot_note;
+    if (!note.two_pass || !d.pilot.p || !d.work.p)
+        return set_err(ctx, RT_ERR_STATE, "rt_debug_last_pilot: the last render launch ran one pass");
+    HIP_OR_RET(ctx, hipSetDevice(d.id));
+    if (d.pending) HIP_OR_RET(ctx, hipEventSynchronize(d.done));
+    const rt::PilotLayout L = rt::pilot_layout((size_t)note.nloc);
+    const uint32_t* dcost = (const uint32_t*)((const char*)d.pilot.p + L.cost);
+    int32_t lp[2] = {0, 0};   // pixels left, pick word
+    if (note.lanes > 0) {
+        HIP_OR_RET(ctx, hipMemcpy(lp, (const char*)d.work.p + rt::kTeamOffset, sizeof lp, hipMemcpyDeviceToHost));
+    } else {
+        // no pick ran: the count kernel over the costs here, on words of this hook's own (the pick word stays 0)
+        HIP_OR_RET(ctx, grow(d, d.scratch_b, sizeof lp));
+        unsigned* left = (unsigned*)d.scratch_b.p;
+        HIP_OR_RET(ctx, rt::launch_pilot_pick(dcost, note.nloc, 1, 0, left, (int*)(left + 1), d.stream));
+        HIP_OR_RET(ctx, hipMemcpyAsync(lp, left, sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_OR_RET(ctx, hipStreamSynchronize(d.stream));
+    }
+    const int64_t v[8] = {1, note.nloc, note.pilot, note.chunk, note.levels, note.lanes, (uint32_t)lp[0], lp[1]};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
+    const size_t bytes = (size_t)std::min<int64_t>(cap, note.nloc) * sizeof(uint32_t);
+    if (bytes) {
+        HIP_OR_RET(ctx, hipMemcpy(cost_out, dcost, bytes, hipMemcpyDeviceToHost));
+        HIP_OR_RET(ctx, hipMemcpy(order_out, (const char*)d.pilot.p + L.order, bytes, hipMemcpyDeviceToHost));
+    }
     return RT_OK;
 }
 

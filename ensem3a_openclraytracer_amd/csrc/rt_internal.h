@@ -210,12 +210,41 @@ struct RenderPending {
     FrameParams b{};          // pass 2's parameters
     bool spec_ok = false;
 };
+// The scratch of a two-pass launch over a tile of n pixels (rt_api.hip setup_pilot; rt_debug_pilot_order sizes its
+// own by the same rule): state 32 B | cost 4 B | order 4 B per pixel, bin totals + offsets (2 x 256), the chunk
+// costs + chunk order (at most one chunk per pixel), the sort's segment histograms (256 per 256 chunks) and each
+// pixel's pass-1 RNG offset (4 B, pilot_draws).  launch_pilot_order lays the words behind the order out itself.
+struct PilotLayout { size_t need, cost, order, draws; };   // bytes; the state is at 0
+inline PilotLayout pilot_layout(size_t n) {
+    const size_t need = n * 40 + 2 * 256 * sizeof(uint32_t) + 2 * (n + 1) * sizeof(uint32_t) +
+                        (n + 256) * sizeof(uint32_t) + n * sizeof(uint32_t);
+    return {need, n * 32, n * 36, need - n * sizeof(uint32_t)};
+}
+// What launch_render remembers of a launch for rt_debug_last_pilot (host integers only): whether it ran two
+// passes and, if so, the tile, the pilot samples, the order's chunk and bins as launch_pilot_order took them, and
+// the resident lanes the pick was given (0: no pick ran -- a set "walk_team", a set "spec", the brute-force path)
+struct PilotNote {
+    int two_pass = 0;
+    int64_t nloc = 0;
+    int pilot = 0, chunk = 0, levels = 0;
+    int64_t lanes = 0;
+};
+// The pass-2 order of a two-pass launch (rt_debug.h rt_debug_pilot_order states it step by step): order[0 .. n) from
+// cost[0 .. n), both on the device; order is followed by the scratch words of pilot_layout (bin totals | offs | chunk
+// costs | chunk order | segment histograms).  Enqueued on `stream`; launch_render and rt_debug_pilot_order run this.
+hipError_t launch_pilot_order(const uint32_t* cost, int64_t n, int chunk, int levels, int pilot, int max_bounce,
+                              uint32_t* order, hipStream_t stream);
+// ... and its pick: *left = the non-zero words of cost[0 .. n), *ts = the pass-2 kernel for that many pixels on
+// `lanes` resident lanes (1, 2 or 4 lanes per pixel; spec: kSpecPick + T trails where teams would be taken)
+hipError_t launch_pilot_pick(const uint32_t* cost, int64_t n, int64_t lanes, int spec, unsigned* left, int* ts,
+                             hipStream_t stream);
 // Launch the render kernel; counts != nullptr selects the instrumented build
 // (device pointer to 5 uint64 accumulators).
 // d_work: kWorkBytes of device scratch (layout above; the counters are zeroed by the launch).
+// note: what rt_debug_last_pilot reports of this launch (may be NULL)
 hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversal, int block,
                          float* d_out, unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream,
-                         RenderPending* pend = nullptr);
+                         RenderPending* pend = nullptr, PilotNote* note = nullptr);
 hipError_t launch_render_finish(const DevScene& sc, int traversal, int block, float* d_out, unsigned int* d_work,
                                 hipStream_t stream, RenderPending& pend);
 // One add of a progressive accumulation (state, base: see above; fp: a one-pass frame, fp.spp = the samples done

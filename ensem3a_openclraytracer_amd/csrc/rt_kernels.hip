@@ -1632,8 +1632,12 @@ __global__ void pilot_chunk_kernel(const uint32_t* __restrict__ cost, int64_t nf
     }
 }
 
+// (the minimum in 64 bits: scale reaches 2^24, so a 32-bit cost's scaled value reaches 2^40, and cut to a word
+// before the minimum it would land in a low bin instead of saturating -- no render's cost gets there, a chunk
+// traces about `top` rays at most, but rt_debug_pilot_order takes any word)
 __device__ __forceinline__ uint32_t cost_bin(uint32_t v, uint32_t scale, uint32_t maxbin) {
-    return min(maxbin, (uint32_t)(((uint64_t)v * scale) >> 16));
+    const uint64_t b = ((uint64_t)v * scale) >> 16;
+    return b < maxbin ? (uint32_t)b : maxbin;
 }
 
 // Stable counting sort of the chunks by cost bin (descending bins, tile order within a bin, so the
@@ -1723,34 +1727,33 @@ static hipError_t launch_pass(const DevScene& sc, const FrameParams& fp, int tra
 // then the rest of each pixel in descending order of the rays its (chunk's) pilot samples traced.  The
 // frame ends when its last-started pixels finish; started last, the cheapest pixels make that tail
 // short.  Every pixel's samples run in the same order as in one pass, so the frame is bit-identical.
-hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
-                         unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, RenderPending* pend) {
-    if (fp.pilot <= 0 || fp.pass != 0 || d_counts || fp.spp <= fp.pilot || fp.nloc <= 0 || !fp.pilot_state)
-        return launch_pass(sc, fp, traversal, block, d_out, d_counts, d_work, stream);
-    FrameParams a = fp;
-    a.pass = 1;
-    hipError_t e = launch_pass(sc, a, traversal, block, d_out, nullptr, d_work, stream);
-    if (e != hipSuccess) return e;
-    // scratch after the pixel order (rt_api.hip setup_pilot): bin totals | offs | chunk costs |
+// The order's chunk and bins as the launch takes them from FrameParams::pilot_chunk / pilot_levels
+static int pilot_chunk_of(int chunk) { return std::max(chunk, 1); }
+static int pilot_levels_of(int levels) { return std::min(std::max(levels, 2), kCostBins); }
+
+// The ordering launches of a two-pass launch: chunk sums, the segmented counting sort, the expansion to pixels
+hipError_t launch_pilot_order(const uint32_t* cost, int64_t n, int chunk_, int levels_, int pilot, int max_bounce,
+                              uint32_t* order, hipStream_t stream) {
+    if (!cost || !order || n <= 0) return hipErrorInvalidValue;
+    // scratch after the pixel order (rt_internal.h pilot_layout): bin totals | offs | chunk costs |
     // chunk order | segment histograms
-    uint32_t* order = const_cast<uint32_t*>(fp.pilot_order);
-    uint32_t* total = order + fp.nloc;
+    uint32_t* total = order + n;
     uint32_t* offs = total + kCostBins;
-    const int chunk = std::max(fp.pilot_chunk, 1);
-    const int64_t nfull = fp.nloc / chunk;
+    const int chunk = pilot_chunk_of(chunk_);
+    const int64_t nfull = n / chunk;
     const int64_t nseg = (nfull + kSortSeg - 1) / kSortSeg;
     uint32_t* ccost = offs + kCostBins;
     uint32_t* corder = ccost + nfull;
     uint32_t* seghist = corder + nfull;
     // `levels` cost bins over a chunk's rays up to 2 (maxBounce + 1) rays per pilot sample per pixel
-    const int levels = std::min(std::max(fp.pilot_levels, 2), kCostBins);
-    const uint64_t top = (uint64_t)chunk * fp.pilot * 2u * (uint64_t)(std::max(fp.max_bounce, 0) + 1);
+    const int levels = pilot_levels_of(levels_);
+    const uint64_t top = (uint64_t)chunk * pilot * 2u * (uint64_t)(std::max(max_bounce, 0) + 1);
     const uint32_t scale = (uint32_t)std::max<uint64_t>(1, ((uint64_t)levels << 16) / std::max<uint64_t>(top, 1));
     const uint32_t maxbin = (uint32_t)levels - 1;
     const unsigned gc = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nfull + 255) / 256, 2048));
-    const unsigned gp = (unsigned)std::min<int64_t>((fp.nloc + 255) / 256, 2048);
+    const unsigned gp = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
     if (nfull > 0) {
-        hipLaunchKernelGGL(pilot_chunk_kernel, dim3(gc), dim3(256), 0, stream, fp.pilot_cost, nfull, chunk, ccost);
+        hipLaunchKernelGGL(pilot_chunk_kernel, dim3(gc), dim3(256), 0, stream, cost, nfull, chunk, ccost);
         hipLaunchKernelGGL(pilot_seg_hist_kernel, dim3((unsigned)nseg), dim3(kSortSeg), 0, stream, ccost, nfull, nseg,
                            scale, maxbin, seghist);
         hipLaunchKernelGGL(pilot_seg_scan_kernel, dim3(kCostBins), dim3(kCostBins), 0, stream, seghist, nseg, total);
@@ -1758,7 +1761,42 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
         hipLaunchKernelGGL(pilot_seg_scatter_kernel, dim3((unsigned)nseg), dim3(kSortSeg), 0, stream, ccost, nfull,
                            nseg, scale, maxbin, seghist, offs, corder);
     }
-    hipLaunchKernelGGL(pilot_expand_kernel, dim3(gp), dim3(256), 0, stream, corder, nfull, chunk, fp.nloc, order);
+    hipLaunchKernelGGL(pilot_expand_kernel, dim3(gp), dim3(256), 0, stream, corder, nfull, chunk, n, order);
+    return hipSuccess;
+}
+
+// Pass 2's team size from the pixels pass 1 left unfinished (pilot_team_count_kernel, pilot_team_pick_kernel)
+hipError_t launch_pilot_pick(const uint32_t* cost, int64_t n, int64_t lanes, int spec, unsigned* left, int* ts,
+                             hipStream_t stream) {
+    if (!cost || !left || !ts || n <= 0) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(left, 0, sizeof(unsigned), stream);
+    if (e != hipSuccess) return e;
+    const unsigned gp = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(pilot_team_count_kernel, dim3(gp), dim3(256), 0, stream, cost, n, left);
+    hipLaunchKernelGGL(pilot_team_pick_kernel, dim3(1), dim3(64), 0, stream, left, lanes, spec ? 1 : 0, ts);
+    return hipSuccess;
+}
+
+hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversal, int block, float* d_out,
+                         unsigned long long* d_counts, unsigned int* d_work, hipStream_t stream, RenderPending* pend,
+                         PilotNote* note) {
+    if (note) *note = PilotNote{};
+    if (fp.pilot <= 0 || fp.pass != 0 || d_counts || fp.spp <= fp.pilot || fp.nloc <= 0 || !fp.pilot_state)
+        return launch_pass(sc, fp, traversal, block, d_out, d_counts, d_work, stream);
+    FrameParams a = fp;
+    a.pass = 1;
+    hipError_t e = launch_pass(sc, a, traversal, block, d_out, nullptr, d_work, stream);
+    if (e != hipSuccess) return e;
+    e = launch_pilot_order(fp.pilot_cost, fp.nloc, fp.pilot_chunk, fp.pilot_levels, fp.pilot, fp.max_bounce,
+                           const_cast<uint32_t*>(fp.pilot_order), stream);
+    if (e != hipSuccess) return e;
+    if (note) {
+        note->two_pass = 1;
+        note->nloc = fp.nloc;
+        note->pilot = fp.pilot;
+        note->chunk = pilot_chunk_of(fp.pilot_chunk);
+        note->levels = pilot_levels_of(fp.pilot_levels);
+    }
     FrameParams b = fp;
     b.pass = 2;
     // small tiles of the BVH2 walk: each pixel's remaining samples as speculative trails (rt_spec.hip):
@@ -1777,12 +1815,12 @@ hipError_t launch_render(const DevScene& sc, const FrameParams& fp, int traversa
         int dev = 0, cus = 0;
         e = hipGetDevice(&dev);
         if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess) e = hipMemsetAsync(left, 0, sizeof(unsigned), stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(pilot_team_count_kernel, dim3(gp), dim3(256), 0, stream, fp.pilot_cost, fp.nloc, left);
         // resident lanes of the one-lane BVH2 walk: 4 waves per SIMD
-        hipLaunchKernelGGL(pilot_team_pick_kernel, dim3(1), dim3(64), 0, stream, left,
-                           (int64_t)std::max(cus, 1) * kWalkLanesPerCu, spec_ok ? 1 : 0, ts);
+        const int64_t lanes = (int64_t)std::max(cus, 1) * kWalkLanesPerCu;
+        e = launch_pilot_pick(fp.pilot_cost, fp.nloc, lanes, spec_ok ? 1 : 0, left, ts, stream);
+        if (e != hipSuccess) return e;
+        if (note) note->lanes = lanes;
         // the pick is read back (pass 1 has to finish before pass 2 anyway) and exactly the kernel it names
         // is launched: 1, 2 or 4 lanes per pixel, or kSpecPick + T trails
         RenderPending local;

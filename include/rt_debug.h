@@ -242,6 +242,44 @@ int rt_debug_last_slices(void);
  * sliced launches), else 0 -- a field of its own: the key's brute is the same with the option on and off. */
 int rt_debug_last_launch(int32_t out[21]);
 
+/* The pass-2 pixel order of a two-pass launch (option "pilot"), computed on device 0 by the launches a render runs
+ * (chunk sums, the segmented counting sort, the expansion to pixels) from the caller's costs; it needs no scene.
+ * cost[n]: the rays each tile pixel traced in pass 1; order_out[n]: the tile pixel pass 2 starts q-th.  The order:
+ *   1. chunks of `chunk` consecutive tile pixels; nfull = n / chunk of them are whole; the sum of a chunk's costs,
+ *      modulo 2^32, is its cost v;
+ *   2. top = chunk * pilot * 2 * (max(max_bounce, 0) + 1), the most rays a chunk's pilot samples can trace;
+ *      scale = max(1, (levels << 16) / max(top, 1)); bin(v) = min(levels - 1, (v * scale) >> 16), the product in
+ *      64 bits;
+ *   3. the whole chunks in descending order of their bin, chunks of one bin in ascending chunk index (stable);
+ *   4. the pixels of a chunk in tile order; the pixels past nfull * chunk keep their place (nfull = 0: the
+ *      identity).
+ * tests/pilot_ref.py restates it.  RT_ERR_ARG, before any launch, for n <= 0, chunk < 1 or > 4096, levels outside
+ * 2..256, pilot < 1 or > 2^20, max_bounce > 4096 (the ranges of the options and of a frame). */
+int rt_debug_pilot_order(rt_ctx* ctx, const uint32_t* cost, int64_t n, int chunk, int levels, int pilot, int max_bounce,
+                         uint32_t* order_out);
+
+/* The pass-2 pick of a two-pass launch, computed on device 0 by the two launches a render runs, from the caller's
+ * costs and for a device that keeps `lanes` lanes of the one-lane walk resident: out[0] = left, the pixels pass 1
+ * left unfinished (cost[p] != 0); out[1] = the pick word:
+ *   k = 4 when 4 left <= 2 lanes, 2 when 4 left <= 4 lanes, else 1 (lanes per pixel);
+ *   spec 0, or k = 1: the word is k;  spec 1 and k > 1: RT_SPEC_PICK + T trails per pixel, T = 8 when 4 left <=
+ *   lanes, else k.
+ * RT_ERR_ARG, before any launch, for n <= 0, lanes < 1 or spec outside 0..1. */
+enum { RT_SPEC_PICK = 10 };
+int rt_debug_pilot_pick(rt_ctx* ctx, const uint32_t* cost, int64_t n, int64_t lanes, int spec, int32_t out[2]);
+
+/* What the last rt_render* / rt_count_work* launch of a single-device context did as a two-pass launch, after that
+ * launch has been waited for (a blocking render, or the stream of rt_render_device synchronised): info[0] = 1 (two
+ * passes ran), info[1] = the tile's pixels nloc, info[2] = the pilot samples per pixel, info[3], info[4] = the
+ * order's chunk and bins, info[5] = the resident lanes the pick was given (0: no pick ran -- "walk_team" or "spec"
+ * set, or the brute-force path), info[6] = left, the pixels pass 1 left unfinished (where no pick ran, counted by
+ * this call), info[7] = the pick word as rt_debug_pilot_pick gives it (0 where no pick ran).  The first min(cap,
+ * nloc) words of the costs pass 1 wrote and of the pass-2 order are copied out of the device's scratch, where they
+ * stay until the context's next launch (both may be NULL when cap is 0).  RT_ERR_STATE when that launch ran one
+ * pass (then nothing is written), RT_ERR_ARG for a context of several devices.  A progressive add is no such
+ * launch and leaves the report as it was. */
+int rt_debug_last_pilot(rt_ctx* ctx, int64_t info[8], uint32_t* cost_out, uint32_t* order_out, int64_t cap);
+
 /* No device call: the rule for the refill threshold of the one-lane brute-force kernels (option "brute_refill" =
  * option: -1 auto, 0 or 1 off, R = 2..64) for a launch over a tile of nloc pixels on a device that keeps `lanes`
  * lanes of the kernel resident.  *out = R, the free lanes a wave waits for before it hands out jobs, or 0 when

@@ -1205,7 +1205,11 @@ def test_stack_lds_entries_render_identically(kl, case):
                                                ("serre_96x54_s4", 64, 2), ("monkey_c3_64_s4", 7, 33)])
 def test_two_pass_pilot_order_options(kl, case, chunk, levels):
     """pilot_chunk / pilot_levels only change the pass-2 order (a stable counting sort of chunks of
-    consecutive pixels by cost bin, partial last chunk in place): every pixel is continued once."""
+    consecutive pixels by cost bin, partial last chunk in place).  What this checks: whatever the order,
+    every pixel is continued exactly once from its own state, so the frame is the oracle's.  What it does
+    not check: the order itself -- any permutation of the pixels gives this frame.  That the order is the
+    descending, stable, saturating one, and what the pick chooses, is checked in
+    tests/test_gpu_pilot_order.py against tests/pilot_ref.py."""
     sc, cam, env, npix, spp, mb, ibl = W.PARITY_CASES[case].inputs()
     try:
         kl.native.set_option("pilot", 2)
