@@ -105,6 +105,40 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+# oracle_state of rt_oracle.c: a work-item before its output stage
+PIXEL_STATE_DTYPE = np.dtype([("sum", np.float32, (3,)), ("seed0", np.uint32), ("seed1", np.uint32),
+                              ("k", np.float32), ("hit", np.int32)])
+
+
+def pixel_state(osc: OracleScene, cam, env, npix: int, spp: int, max_bounce: int, first: int = 0,
+                count: int = None):
+    """Pixels ``first .. first+count-1``: (a ``PIXEL_STATE_DTYPE`` array -- the unclamped sample sum, the
+    RNG words after the last sample, the camera hit -- and their frame values float32 [3*count])."""
+    cam, env = _f32(cam), _f32(env)
+    count = npix - first if count is None else count
+    st = np.zeros(max(count, 1), PIXEL_STATE_DTYPE)
+    out = np.zeros(3 * max(count, 1), np.float32)
+    rc = lib().oracle_pixel_state(ctypes.byref(osc.c), ctypes.c_void_p(cam.ctypes.data),
+                                  ctypes.c_void_p(env.ctypes.data), ctypes.c_int32(npix), ctypes.c_int32(spp),
+                                  ctypes.c_int32(max_bounce), ctypes.c_int32(first), ctypes.c_int32(count),
+                                  ctypes.c_void_p(st.ctypes.data), ctypes.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise ValueError("oracle_pixel_state: bad arguments")
+    return st[:count], out[:3 * count]
+
+
+def gi_sample(osc: OracleScene, cam, env, max_bounce: int, pixel: int, seeds):
+    """One ``naiveGI`` call on pixel ``pixel``'s camera hit from ``seeds`` = (seed0, seed1);
+    returns (colour float32 [3], seeds after)."""
+    cam, env = _f32(cam), _f32(env)
+    io = np.array(seeds, dtype=np.uint32)
+    col = np.zeros(3, np.float32)
+    lib().oracle_gi_sample(ctypes.byref(osc.c), ctypes.c_void_p(cam.ctypes.data), ctypes.c_void_p(env.ctypes.data),
+                           ctypes.c_int32(max_bounce), ctypes.c_int32(pixel), ctypes.c_void_p(io.ctypes.data),
+                           ctypes.c_void_p(col.ctypes.data))
+    return col, (int(io[0]), int(io[1]))
+
+
 def rand_stream(seed0: int, seed1: int, n: int):
     out = np.zeros(n, np.float32)
     st = np.zeros(2, np.uint32)

@@ -3,7 +3,9 @@
 // the reference sources it includes (-I <reference>/Kernels); nothing from the
 // reference is copied here.  Each kernel evaluates one reference function per
 // work-item on host-provided inputs so the CPU oracle can be pinned to the
-// reference implementation as executed by the ROCm OpenCL runtime.
+// reference implementation as executed by the ROCm OpenCL runtime
+// (_ref/kat_gfx950.co, oracle/refcl.py) and, compiled for the host with the
+// builtins of ref_cl/cpu_shim.c, on the CPU (_ref/librefcpu.so, oracle/refcpu.py).
 #include "Raytracing.cl"
 
 __kernel void kat_rand(__global const uint* seeds, const int nd, __global float* out, __global uint* st) {
@@ -130,6 +132,53 @@ __kernel void kat_math(const int fn, __global const float* x, __global const flo
         default: break;
     }
     out[t] = r;
+}
+
+// What the Raytracing kernel holds for pixel i before its output stage: the
+// reference's own sequence (Raytracing.cl:170-209) with the kernel's seed
+// initialisation, then the UNCLAMPED sample sum, the RNG words after the last
+// sample and the camera hit.  The frame divides and clamps, so a saturated pixel
+// hides its sum, and the frame never shows the RNG words at all.
+__kernel void kat_pixel_state(__constant float* vertex_p, __constant float* vertex_n, __constant float* vertex_uv,
+                              __constant int* face_data, __global float* mat, __constant float* BVH,
+                              __global float* cam, __global float* envData, const int triCount, const int imgSize,
+                              const int maxSpp, const int maxBounce, __read_only image2d_t IBL,
+                              __global float* sum, __global uint* seeds, __global float* hit) {
+    int i = get_global_id(0);
+    unsigned int seed0 = i % imgSize;
+    unsigned int seed1 = i / imgSize;
+    const sampler_t sampler = CLK_NORMALIZED_COORDS_FALSE | CLK_ADDRESS_CLAMP_TO_EDGE | CLK_FILTER_LINEAR;
+    ray r = genCameraRay(i, cam);
+    hitInfo H = rayTrace(r, vertex_p, vertex_n, vertex_uv, face_data, triCount, BVH);
+    material M = extractMaterial(mat, H.mat);
+    float3 output = (float3)(0.0f);
+    for (int s = 0; s < maxSpp; ++s) {
+        output += naiveGI((float3)(1.0f), maxBounce, triCount, H, r, M, IBL, sampler, mat, vertex_p, vertex_n,
+                          vertex_uv, face_data, BVH, &seed0, &seed1, envData);
+    }
+    sum[3 * i + 0] = output.x; sum[3 * i + 1] = output.y; sum[3 * i + 2] = output.z;
+    seeds[2 * i + 0] = seed0; seeds[2 * i + 1] = seed1;
+    hit[2 * i + 0] = H.k; hit[2 * i + 1] = H.bHit ? 1.0f : 0.0f;
+}
+
+// One naiveGI call on the camera hit and material of pixel idx[t], from the
+// caller's seeds; returns the colour and the seeds after.  The reference-side
+// counterpart of oracle_sample_trail, for locating a difference.
+__kernel void kat_gi_sample(__constant float* vertex_p, __constant float* vertex_n, __constant float* vertex_uv,
+                            __constant int* face_data, __global float* mat, __constant float* BVH,
+                            __global float* cam, __global float* envData, const int triCount, const int maxBounce,
+                            __read_only image2d_t IBL, __global const int* idx, __global uint* seeds,
+                            __global float* out) {
+    int t = get_global_id(0);
+    unsigned int seed0 = seeds[2 * t], seed1 = seeds[2 * t + 1];
+    const sampler_t sampler = CLK_NORMALIZED_COORDS_FALSE | CLK_ADDRESS_CLAMP_TO_EDGE | CLK_FILTER_LINEAR;
+    ray r = genCameraRay(idx[t], cam);
+    hitInfo H = rayTrace(r, vertex_p, vertex_n, vertex_uv, face_data, triCount, BVH);
+    material M = extractMaterial(mat, H.mat);
+    float3 c = naiveGI((float3)(1.0f), maxBounce, triCount, H, r, M, IBL, sampler, mat, vertex_p, vertex_n,
+                       vertex_uv, face_data, BVH, &seed0, &seed1, envData);
+    out[3 * t + 0] = c.x; out[3 * t + 1] = c.y; out[3 * t + 2] = c.z;
+    seeds[2 * t] = seed0; seeds[2 * t + 1] = seed1;
 }
 
 // SampleSphericalMap alone (MathLib.cl:72-80): the direction -> uv mapping of

@@ -13,7 +13,10 @@
  * this oracle and the HIP reference-order traversal are bit-comparable; the
  * oracle is pinned against the reference kernel itself (compiled by ROCm's
  * OpenCL compiler and run by the ROCm OpenCL runtime, oracle/ref_cl/) through
- * the golden fixtures in tests/golden/.
+ * the golden fixtures in tests/golden/, and must equal the reference's kernel
+ * text compiled for the host over rtm.h's builtins (oracle/refcpu.py) bit for
+ * bit: whole frames, per-pixel state and function by function
+ * (tests/test_reference_cpu.py).
  *
  * Build: oracle/Makefile (gcc -O2 -march=x86-64-v3 -ffp-contract=off -fopenmp).
  */
@@ -371,9 +374,14 @@ static float3 naiveGI(float3 sampleOut, int maxBounce, hitInfo H_cam, ray R_cam,
     return sampleOut;
 }
 
+/* What a work-item holds before its output stage (oracle_pixel_state): the unclamped sample sum, the
+ * RNG words after the last sample, the camera hit's k and hit flag. */
+typedef struct { float sum[3]; uint32_t seed0, seed1; float k; int32_t hit; } oracle_state;
+
 /* ---- Raytracing.cl:161-221, one work-item ---- */
 static void raytracing_pixel(const oracle_scene* sc, const float* cam, const float* envData, int i,
-                             int imgSize, int maxSpp, int maxBounce, float* out3, oracle_counts* cnt) {
+                             int imgSize, int maxSpp, int maxBounce, float* out3, oracle_counts* cnt,
+                             oracle_state* state) {
     uint32_t seed0 = (uint32_t)(i % imgSize);
     uint32_t seed1 = (uint32_t)(i / imgSize);
     float3 output = rtm_v3(0, 0, 0);
@@ -387,6 +395,11 @@ static void raytracing_pixel(const oracle_scene* sc, const float* cam, const flo
                                          sc, &seed0, &seed1, envData, cnt);
         output = rtm_add(output, baseColor);
         log_event(3.0f, spp, rtm_v3(0, 0, 0), rtm_v3(0, 0, 0), NULL, baseColor);
+    }
+    if (state) {
+        state->sum[0] = output.x; state->sum[1] = output.y; state->sum[2] = output.z;
+        state->seed0 = seed0; state->seed1 = seed1;
+        state->k = H_cam_cache.k; state->hit = H_cam_cache.bHit;
     }
     output = rtm_div(output, (float)maxSpp);
     out3[0] = rtm_fmax(rtm_fmin(output.x, 1.0f), 0.0f);
@@ -422,7 +435,7 @@ int oracle_render(const oracle_scene* sc, const float* cam, const float* env, in
             const int k = (int)(p / W), c = (int)(p % W);
             const int i = (row0 + k * row_step) * W + c;
             if (i >= npix) continue;
-            raytracing_pixel(sc, cam, env, i, npix, spp, max_bounce, out + 3 * p, counts ? &local : NULL);
+            raytracing_pixel(sc, cam, env, i, npix, spp, max_bounce, out + 3 * p, counts ? &local : NULL, NULL);
         }
         if (counts) {
 #if defined(_OPENMP)
@@ -443,10 +456,32 @@ int oracle_render(const oracle_scene* sc, const float* cam, const float* env, in
 int oracle_pixel_log(const oracle_scene* sc, const float* cam, const float* env, int32_t npix, int32_t spp,
                      int32_t max_bounce, int32_t i, float* log, int32_t cap, float* out3) {
     g_log = log; g_log_cap = cap; g_log_n = 0;
-    raytracing_pixel(sc, cam, env, i, npix, spp, max_bounce, out3, NULL);
+    raytracing_pixel(sc, cam, env, i, npix, spp, max_bounce, out3, NULL, NULL);
     const int n = g_log_n;
     g_log = NULL; g_log_cap = 0; g_log_n = 0;
     return n;
+}
+
+/* Pixels first .. first+count-1 of the frame of npix pixels, each as raytracing_pixel leaves it before the
+ * output stage: state[count] (the frame shows neither a clamped pixel's sum nor the RNG words) and the
+ * frame values out[3*count].  Returns 0, or -1 on bad arguments. */
+int oracle_pixel_state(const oracle_scene* sc, const float* cam, const float* env, int32_t npix, int32_t spp,
+                       int32_t max_bounce, int32_t first, int32_t count, oracle_state* state, float* out) {
+    if ((int)cam[6] <= 0 || npix <= 0 || first < 0 || count < 0) return -1;
+    for (int32_t t = 0; t < count; ++t)
+        raytracing_pixel(sc, cam, env, first + t, npix, spp, max_bounce, out + 3 * t, NULL, state + t);
+    return 0;
+}
+
+/* One naiveGI call on the camera hit and material of pixel i from the caller's RNG words (updated in
+ * place): what kat_gi_sample (oracle/ref_cl/kat.cl) asks of the reference. */
+void oracle_gi_sample(const oracle_scene* sc, const float* cam, const float* env, int32_t max_bounce, int32_t i,
+                      uint32_t* io_seeds, float* col3) {
+    const ray r = genCameraRay(i, cam);
+    const hitInfo H = rayTrace(sc, r, NULL);
+    const material M = extractMaterial(sc->mat, H.mat);
+    const float3 o = naiveGI(rtm_v3(1.0f, 1.0f, 1.0f), max_bounce, H, r, M, sc, &io_seeds[0], &io_seeds[1], env, NULL);
+    col3[0] = o.x; col3[1] = o.y; col3[2] = o.z;
 }
 
 /* One sample of pixel i as a function of its RNG offset: for every even offset D = 2p < 2P (draws

@@ -1489,19 +1489,25 @@ def _random_scene(seed, ntri):
                                  materialData=mat.ravel(), lightData=np.zeros(0, np.float32), BVH=B.BVH(fd, vp.ravel()))
 
 
+def _random_scene_config(seed):
+    """(cam, env, npix, spp, max_bounce) of soup `seed` (also tests/test_reference_cpu.py and
+    tests/test_gpu_reference.py): camera at (0, -3.5, 0), rotated a little, a random field of view; sun
+    direction, sun and IBL power and bounce count vary per seed (IBL power 0 / sun power 0 included: the
+    shortcuts that skip them)."""
+    rng = np.random.default_rng(7000 + seed)
+    cam = np.array([0.0, -3.5, 0.0, *rng.uniform(-12.0, 12.0, 3), 40, 40, 1,
+                    float(rng.choice([30.0, 45.0, 75.0])) * (3.14 / 180)], np.float64).astype(np.float32)
+    env = np.array([*rng.uniform(-180.0, 180.0, 3), rng.choice([0.0, 0.5, 2.0]), rng.choice([0.0, 0.3, 1.0])],
+                   np.float64).astype(np.float32)
+    return cam, env, 40 * 40, 4, int(rng.choice([0, 1, 2, 4, 7]))
+
+
 @pytest.mark.parametrize("seed,ntri", RANDOM_SCENES)
 def test_random_scenes_match_oracle(kl, seed, ntri):
     import json
     sc = _random_scene(seed, ntri)
     ibl = W.ibl_preview()
-    rng = np.random.default_rng(7000 + seed)
-    # camera at (0, -3.5, 0), rotated a little, a random field of view; sun direction, sun and IBL power and
-    # bounce count vary per seed (IBL power 0 / sun power 0 included: the shortcuts that skip them)
-    cam = np.array([0.0, -3.5, 0.0, *rng.uniform(-12.0, 12.0, 3), 40, 40, 1,
-                    float(rng.choice([30.0, 45.0, 75.0])) * (3.14 / 180)], np.float64).astype(np.float32)
-    env = np.array([*rng.uniform(-180.0, 180.0, 3), rng.choice([0.0, 0.5, 2.0]), rng.choice([0.0, 0.3, 1.0])],
-                   np.float64).astype(np.float32)
-    npix, spp, mb = 40 * 40, 4, int(rng.choice([0, 1, 2, 4, 7]))
+    cam, env, npix, spp, mb = _random_scene_config(seed)
     ora = _oracle(sc, cam, env, npix, spp, mb, ibl)
     ref = _launch(kl, sc, cam, env, npix, spp, mb, ibl, "ref")
     np.testing.assert_array_equal(ref, ora)

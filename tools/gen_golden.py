@@ -11,6 +11,13 @@ Known-answer tests call the reference's device functions through oracle/ref_cl/k
 Outputs: ref_<case>.npz per parity case (inputs spec + reference image + kernel ms),
 kat_reference.npz (inputs and outputs of every KAT), ref_timing.json (reference
 kernel time at the benchmark configs on this GPU).
+
+    python tools/gen_golden.py --cpu OUTDIR
+
+The CPU section: needs no GPU and no OpenCL runtime, only oracle/_ref/librefcpu.so (the
+reference's kernel text compiled for the host, oracle/refcpu.py).  Writes
+ref_cpu_frames.npz: the reference's frames of the parity cases, kat_pixel_state of four of
+them and a meta JSON with the compiler version and flags.
 """
 import json
 import os
@@ -177,5 +184,34 @@ def main(outdir):
         json.dump(timing, f, indent=1)
 
 
+def main_cpu(outdir):
+    """ref_cpu_frames.npz: the reference's kernel text compiled for the host (oracle/_ref/librefcpu.so,
+    oracle/refcpu.py) on the parity cases -- its frames, and kat_pixel_state of refcpu.GOLDEN_STATE_CASES.
+    Needs no GPU and no OpenCL runtime, only `make -C oracle ref` where the reference tree exists."""
+    from oracle import refcpu
+    os.makedirs(outdir, exist_ok=True)
+    assert refcpu.available(), "oracle/_ref/librefcpu.so is not built (make -C oracle ref where the reference exists)"
+    res = refcpu.golden_frames()
+    meta = dict(refcpu.build_info(), generator="tools/gen_golden.py --cpu", time=time.strftime("%Y-%m-%d %H:%M:%S"),
+                cases=list(W.PARITY_CASES), state_cases=list(refcpu.GOLDEN_STATE_CASES))
+    res["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+    path = os.path.join(outdir, "ref_cpu_frames.npz")
+    np.savez_compressed(path, **res)
+    print(f"{path}: {os.path.getsize(path)} bytes, {len(res) - 1} arrays", flush=True)
+
+
+def _cpu_outdir(argv):
+    """OUTDIR of `--cpu OUTDIR` (either order), or None when --cpu is not given."""
+    if "--cpu" not in argv:
+        return None
+    rest = [a for a in argv if a != "--cpu"]
+    if len(rest) != 1:
+        sys.exit("usage: python tools/gen_golden.py --cpu OUTDIR")
+    return rest[0]
+
+
 if __name__ == "__main__":
+    if _cpu_outdir(sys.argv[1:]) is not None:
+        main_cpu(_cpu_outdir(sys.argv[1:]))
+        sys.exit(0)
     main(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/golden")
